@@ -10,6 +10,13 @@ evaluation are sharded over the ranks and one RCCL all-reduce of
 (sum q, sum q^2) gives the trace -- strong scaling of a fixed evaluation.
 
 Prints ONE JSON line on rank 0 (contract in the task statement).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up,
+times the K evaluations, writes the last evaluation's outputs if
+--dump-outputs DIR is given and prints the line.  Everything else the line
+can carry -- the launch profiler's roofline and its isolated passes, the
+mc_trace leg, the reference composition, the CPU baselines, the error against
+the reference trace -- runs only with --full.
 """
 from __future__ import annotations
 
@@ -68,6 +75,17 @@ def parse():
                     help="all-gather the per-probe forms and sum them in global probe order on every "
                          "rank (SURVEY §8e): the estimate is bit-identical for any number of ranks")
     ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the launch profiler and the roofline passes, "
+                         "the mc_trace leg beside a Hutchinson headline, the reference composition, the CPU "
+                         "baselines and the comparison with the reference trace.  Without it the run sets up, "
+                         "warms up, times --steps evaluations and prints the line (--cpu-seconds, --mc-steps, "
+                         "--ref-cpu-seconds and the profiler are then off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed evaluation returned as DIR/<name>.npy "
+                         "(float64; rank 0): q = this rank's per-probe quadratic forms and moments = (sum q, "
+                         "sum (q - mean)^2) over all ranks for the Hutchinson estimator, mc_trace = (estimate, "
+                         "residual, rounds) for --estimator mc_trace")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N > 1 (nccl = RCCL over xGMI; gloo only to "
                          "rehearse the multi-rank path, e.g. several ranks sharing one GPU with "
@@ -301,6 +319,12 @@ def main():
         sys.exit(rc)
     if args.steps is None:
         args.steps = 100 if args.config == "er100k" else 5
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if not args.full:  # a plain run: only what the headline figure needs
+        args.no_profile = True
+        args.cpu_seconds = args.ref_cpu_seconds = 0.0
+        args.mc_steps = 0
     if args.lanes == 0:
         args.lanes = 3 if args.explicit else 2
     os.environ["KT_SLQ_LANES"] = str(args.lanes)
@@ -343,15 +367,17 @@ def main():
     if args.bitstable:
         off, cnt = kdist.probe_shard_aligned(N, P, rank, world)
         counts = [kdist.probe_shard_aligned(N, P, r, world)[1] for r in range(world)]
-    ref = reference_trace(args.config, args.weighted) if m >= 20 else None
+    ref = reference_trace(args.config, args.weighted) if args.full and m >= 20 else None
 
     def submit(seed):
         return kra.slq_submit(D, cnt, m, seed=seed, probe_offset=off, block=P, ctx=ctx)
 
     coll_stats = {}
+    last = {}  # what the latest evaluation returned (--dump-outputs)
 
     def finish(pending):
         _, _, q = kra.slq_collect(pending)
+        last["q"] = q
         if args.bitstable:  # every rank reduces all N forms in global probe order
             return kdist.bitstable_sums(q, counts)
         # ONE collective per evaluation: all-gather of (count, sum, M2), Chan's
@@ -561,6 +587,14 @@ def main():
     # distinct GPUs: a one-device rehearsal (every rank on GPU 0) is 1 GPU
     one_dev = os.environ.get("KT_BENCH_ONE_DEVICE") == "1"
     n_devices = 1 if one_dev else (pg_world if use_pg else world)
+    if rank == 0 and args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        if run_hutch:  # the last timed evaluation: its forms (this rank's shard) and the reduced moments
+            dump = {"q": last["q"], "moments": sums[-1]}
+        else:
+            dump = {"mc_trace": (extra["trace_estimate"], extra["res"], extra["rounds"])}
+        for name, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float64))
     if rank == 0:
         cfg = {"workload": wl, "n": n, "nnz": nnz, "lanczos_m": m, "fun": "exp"}
         if run_hutch:

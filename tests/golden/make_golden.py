@@ -144,7 +144,25 @@ def main_v73():
         json.dump(vals, f, indent=1)
 
 
+def main_mat():
+    """The MAT-files tests/test_matv73.py reads, under datasets_paper/ here with
+    the reference's own layout: the three MAT v7.3 datasets as they are (data
+    files, each well under 1 MiB) and, because Transport/Hawaii.mat is 2.4 MB,
+    a compressed MAT v5 file with its Problem.A alone."""
+    import shutil
+    for name in V73:
+        dst = os.path.join(HERE, "datasets_paper", "Misc", name + ".mat")
+        os.makedirs(os.path.dirname(dst), exist_ok=True)
+        shutil.copyfile(os.path.join(REF, "datasets_paper", "Misc", name + ".mat"), dst)
+    P = sio.loadmat(os.path.join(REF, "datasets_paper", "Transport", "Hawaii.mat"))["Problem"]
+    dst = os.path.join(HERE, "datasets_paper", "Transport", "Hawaii.mat")
+    os.makedirs(os.path.dirname(dst), exist_ok=True)
+    sio.savemat(dst, {"Problem": {"A": sp.csc_matrix(P["A"][0, 0])}}, do_compression=True, format="5")
+
+
 def main():
+    if "--mat" in sys.argv:
+        return main_mat()
     if "--hawaii" in sys.argv:
         return main_hawaii()
     if "--v73" in sys.argv:

@@ -8,13 +8,15 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-SMALL = ["--config", "er100k", "--nprobes", "32", "--lanczos-m", "5", "--steps", "2", "--warmup", "1"]
+PLAIN = ["--config", "er100k", "--nprobes", "32", "--lanczos-m", "5", "--steps", "2", "--warmup", "1"]
+SMALL = [*PLAIN, "--full"]  # the legs beside the headline (profiler, mc_trace, CPU baseline) run with --full
 KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
         "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"}
 
@@ -68,6 +70,40 @@ def test_bench_single_process_line():
     assert d["yform_redone_sweeps"] == 0
     assert d["collective"] is None  # single process, no torchrun: no process group
     assert roof["busy_within_timed_region"] is True
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) carries the contract's fields and none of the
+    legs beside the headline; --steps sets the timed evaluations (one estimate
+    each); --dump-outputs writes the last timed evaluation's per-probe forms
+    and moments, which a second run (here with --full: same seeds, same
+    probes) reproduces bit for bit."""
+    outs = []
+    for k, extra in enumerate((["--steps", "3"], ["--full", "--cpu-seconds", "0", "--mc-steps", "0",
+                                                  "--steps", "3"])):
+        dump = tmp_path / f"dump{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", *PLAIN, *extra,
+                            "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1
+        outs.append((lines[0], np.load(dump / "q.npy"), np.load(dump / "moments.npy")))
+    d, q, mom = outs[0]
+    assert KEYS <= set(d)
+    assert d["steps"] == 3 and len(d["evaluations"]["estimates"]) == 3 and d["warmup"] == 1
+    assert d["value"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f64" and d["unit"] == "evals/s"
+    assert d["value"] == pytest.approx(1e3 / d["ms_per_step"], rel=1e-2)
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    assert "mc_trace" not in d and "reference_trace" not in d
+    assert q.dtype == np.float64 and q.shape == (32,) and mom.dtype == np.float64 and mom.shape == (2,)
+    # the dumped forms are the last evaluation's: their mean is the line's estimate
+    assert q.sum() / 32 == pytest.approx(d["trace_estimate"], rel=1e-13)
+    assert mom[0] / 32 == pytest.approx(d["trace_estimate"], rel=1e-15)
+    for d2, q2, mom2 in outs[1:]:
+        np.testing.assert_array_equal(q2, q)
+        np.testing.assert_array_equal(mom2, mom)
+        assert d2["trace_estimate"] == d["trace_estimate"]
+    assert outs[1][0]["roofline"] is not None
 
 
 def _single_line(*extra):

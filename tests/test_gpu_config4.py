@@ -105,7 +105,7 @@ def test_config4_weighted(fx, graph, gpu_ctx):
 
 def test_bench_mc_trace_line_rel_err():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--estimator", "mc_trace",
-                        "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-profile"],
+                        "--full", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--no-profile"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

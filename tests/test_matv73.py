@@ -6,8 +6,10 @@ tests/golden/v73_values.json (make_golden.py --v73), and independently
 against the file's own redundancy -- CollegeMsg stores its 59,835 temporal
 edges beside Problem.A, and accumulating them must reproduce A entry for
 entry (multiplicities included); Drugs/as_735 store the same matrix twice
-(Problem.A and W).  Tests that read /root/reference skip where it is absent
-(the GPU box); the committed prepared graphs are checked everywhere."""
+(Problem.A and W).  The MAT-files are fixtures under tests/golden/datasets_paper
+(make_golden.py --mat: the three v7.3 files as the reference ships them, and
+Transport/Hawaii.mat's Problem.A in a compressed MAT v5 file), so every test
+here runs wherever the repository is checked out."""
 import json
 import os
 
@@ -18,8 +20,7 @@ import scipy.sparse.csgraph as csg
 
 from conftest import GOLDEN, load_v73_graph
 
-REF = "/root/reference/datasets_paper"
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference datasets absent")
+REF = os.path.join(GOLDEN, "datasets_paper")
 NAMES = ["Drugs", "as_735", "CollegeMsg"]
 
 
@@ -34,7 +35,6 @@ def _sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
-@needs_ref
 @pytest.mark.parametrize("name", NAMES)
 def test_reader_digests(name, vals):
     from krylov_robustness_amd import datasets as ds
@@ -51,7 +51,6 @@ def test_reader_digests(name, vals):
     assert isinstance(P["name"], str) and P["name"] == rec["name"]
 
 
-@needs_ref
 def test_collegemsg_temporal_edges_rebuild_A():
     from krylov_robustness_amd import matv73
     P = matv73.loadmat(os.path.join(REF, "Misc", "CollegeMsg.mat"))["Problem"]
@@ -64,7 +63,6 @@ def test_collegemsg_temporal_edges_rebuild_A():
     assert P["kind"] == "directed temporal multigraph"
 
 
-@needs_ref
 @pytest.mark.parametrize("name", ["Drugs", "as_735"])
 def test_struct_fields_and_duplicate_matrix(name):
     from krylov_robustness_amd import matv73
@@ -76,7 +74,6 @@ def test_struct_fields_and_duplicate_matrix(name):
     assert 0.0 < float(d["modularity_NL"][0, 0]) < 1.0
 
 
-@needs_ref
 @pytest.mark.parametrize("name", NAMES)
 def test_prepared_graph_matches_fixture(name):
     from krylov_robustness_amd import datasets as ds
@@ -85,7 +82,6 @@ def test_prepared_graph_matches_fixture(name):
     assert A.shape == G.shape and abs(A - G).max() == 0
 
 
-@needs_ref
 def test_load_variable_v5_struct():
     """MAT v5 files go through scipy with the same dict shape."""
     from krylov_robustness_amd import datasets as ds

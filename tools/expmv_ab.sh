@@ -16,7 +16,7 @@ for rep in 1 2; do
     done
 done
 for v in $NAMES; do
-    KT_LIB=$(lib $v) timeout -k 10 300 python bench.py --cpu-seconds 0 --ref-cpu-seconds 0 > $O/bench_$v.json 2> $O/bench_$v.err \
+    KT_LIB=$(lib $v) timeout -k 10 300 python bench.py --full --cpu-seconds 0 --ref-cpu-seconds 0 > $O/bench_$v.json 2> $O/bench_$v.err \
         || { tail -20 $O/bench_$v.err; exit 1; }
     echo "$v $(cut -c1-200 $O/bench_$v.json)"
 done

@@ -22,6 +22,7 @@
 # Every GPU step has its own time limit; the script stops at the first failure.
 set -o pipefail
 TASK=$1; TAG=${2:-dev}; shift 2 || true
+REPO=$PWD
 O=$PWD/gpurun_out/$TAG; mkdir -p $O
 export TMPDIR=/tmp
 case $TASK in
@@ -33,10 +34,10 @@ smoke)
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
     tail -1 $O/smoke.log ;;
 bench)
-    timeout -k 10 400 python -u bench.py "$@" > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
-    timeout -k 10 400 python -u bench.py --weighted --cpu-seconds 0 > $O/bench_weighted.json 2> $O/bench_weighted.err || { tail -20 $O/bench_weighted.err; exit 1; }
-    timeout -k 10 400 python -u bench.py --estimator mc_trace --steps 20 --cpu-seconds 0 > $O/bench_mc_trace.json 2> $O/bench_mc_trace.err || { tail -20 $O/bench_mc_trace.err; exit 1; }
-    timeout -k 10 400 python -u bench.py --config er100k --steps 100 --warmup 5 --cpu-seconds 5 > $O/bench_er100k.json 2> $O/bench_er100k.err || { tail -20 $O/bench_er100k.err; exit 1; }
+    timeout -k 10 400 python -u bench.py --full "$@" > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+    timeout -k 10 400 python -u bench.py --full --weighted --cpu-seconds 0 > $O/bench_weighted.json 2> $O/bench_weighted.err || { tail -20 $O/bench_weighted.err; exit 1; }
+    timeout -k 10 400 python -u bench.py --full --estimator mc_trace --steps 20 --cpu-seconds 0 > $O/bench_mc_trace.json 2> $O/bench_mc_trace.err || { tail -20 $O/bench_mc_trace.err; exit 1; }
+    timeout -k 10 400 python -u bench.py --full --config er100k --steps 100 --warmup 5 --cpu-seconds 5 > $O/bench_er100k.json 2> $O/bench_er100k.err || { tail -20 $O/bench_er100k.err; exit 1; }
     for f in bench_default bench_weighted bench_mc_trace bench_er100k; do echo "== $f"; cut -c1-300 $O/$f.json; done ;;
 configs)
     for s in bench_config1 bench_config3 bench_greedy bench_hessian; do
@@ -45,7 +46,7 @@ configs)
     done ;;
 prof)
     ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o def \
-        -- python3 $GRAFT_REPO_ROOT/bench.py "$@" > $O/bench.json 2> $O/bench.err ) || { tail -20 $O/bench.err; exit 1; }
+        -- python3 $REPO/bench.py --full "$@" > $O/bench.json 2> $O/bench.err ) || { tail -20 $O/bench.err; exit 1; }
     cp $(find $O/stats -name "*kernel_stats.csv") $O/kernel_stats.csv
     python3 tools/reconcile_trace.py $(find $O/stats -name "*kernel_trace.csv") $O/bench.json $O/reconcile.json || exit 1
     rm -f $(find $O/stats -name "*kernel_trace.csv")
@@ -53,7 +54,7 @@ prof)
 timeline)
     # kernel trace of the er100k bench (config 2), evaluation by evaluation
     ( cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/tl -o tl \
-        -- python3 $GRAFT_REPO_ROOT/bench.py --config er100k --steps 100 --warmup 5 --cpu-seconds 0 --mc-steps 0 "$@" \
+        -- python3 $REPO/bench.py --full --config er100k --steps 100 --warmup 5 --cpu-seconds 0 --mc-steps 0 "$@" \
         > $O/bench_er100k_traced.json 2> $O/tl.err ) || { tail -20 $O/tl.err; exit 1; }
     python3 tools/eval_timeline.py $(find $O/tl -name "*kernel_trace.csv") ${SWEEPS:-2} 100 $O/er100k_eval_timeline.json || exit 1
     gzip -f $(find $O/tl -name "*kernel_trace.csv") ;;
@@ -71,19 +72,19 @@ secondary)
 mctl)
     # kernel trace of the mc_trace leg (trace_exp, Lanczos-exp Afun), evaluation by evaluation
     ( cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/mctl -o mctl \
-        -- python3 $GRAFT_REPO_ROOT/bench.py --estimator mc_trace --steps 10 --cpu-seconds 0 --ref-cpu-seconds 0 \
+        -- python3 $REPO/bench.py --full --estimator mc_trace --steps 10 --cpu-seconds 0 --ref-cpu-seconds 0 \
         --no-profile "$@" > $O/bench_mc_traced.json 2> $O/mctl.err ) || { tail -20 $O/mctl.err; exit 1; }
     python3 tools/mc_timeline.py $(find $O/mctl -name "*kernel_trace.csv") 10 $O/mc_timeline.json || exit 1
     gzip -f $(find $O/mctl -name "*kernel_trace.csv") ;;
 rehearse)
     # the driver's N = 2 command as it may run it (no torchrun: bench.py starts
     # the ranks itself), both ranks on GPU 0 over gloo, default config
-    KT_BENCH_ONE_DEVICE=1 timeout -k 10 500 python -u bench.py --gpus 2 --dist-backend gloo "$@" \
+    KT_BENCH_ONE_DEVICE=1 timeout -k 10 500 python -u bench.py --full --gpus 2 --dist-backend gloo "$@" \
         > $O/bench_2ranks_self_launch.json 2> $O/bench_2ranks_self_launch.err || { tail -20 $O/bench_2ranks_self_launch.err; exit 1; }
     cut -c1-400 $O/bench_2ranks_self_launch.json ;;
 pmc)
     SEC=${SECTION:-sf1m}
-    B="$GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --cpu-seconds 0 --lanes 1 --mc-steps 1 --no-profile $*"
+    B="$REPO/bench.py --full --steps 1 --warmup 1 --cpu-seconds 0 --lanes 1 --mc-steps 1 --no-profile $*"
     R="spmm_dot|spmm_lanczos|k_update"
     ( cd /tmp && timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$R" -d $O/pmc_fetch -o f --output-format csv -- python3 $B > $O/pmc_fetch.log 2>&1 ) || { tail -20 $O/pmc_fetch.log; exit 1; }
     ( cd /tmp && timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$R" -d $O/pmc_write -o w --output-format csv -- python3 $B > $O/pmc_write.log 2>&1 ) || { tail -20 $O/pmc_write.log; exit 1; }

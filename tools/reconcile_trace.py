@@ -1,4 +1,4 @@
-"""Split a rocprofv3 kernel trace of the default bench command into the timed
+"""Split a rocprofv3 kernel trace of the bench command with every leg (`bench.py --full`) into the timed
 region and the isolated single-lane roofline pass, for the dominant kernel,
 and compare each with the bench line it produced.
 Usage: python tools/reconcile_trace.py KERNEL_TRACE_CSV BENCH_JSON OUT_JSON"""
@@ -40,7 +40,7 @@ def main(trace_csv, bench_json, out_json):
     # union of the timed region's launch intervals (lane overlap counted once)
     union = _union([(int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows[-iso - timed:-iso]])
     out = {
-        "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py (default command)",
+        "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full (default configuration)",
         "kernel": kname,
         "bench_value": b["value"],
         "launches_total": len(dur),

@@ -32,6 +32,15 @@ namespace {
 constexpr int kMaxPairs = 256;  // candidates per device batch (512 columns)
 constexpr int64_t kFusedMaxN = 16384;  // the fused one-workgroup-per-candidate path up to this n
 
+// Whether the candidates run one workgroup each (launch_pair_fused: the whole
+// trace_fun_update in one launch): small n and an LDS-sized step limit;
+// KT_PAIRS_FUSED=0 and KT_PAIRS_HOST keep the batched steps.  Read per call.
+bool pairs_fused_applies(int64_t n, int it) {
+    const char* fz = getenv("KT_PAIRS_FUSED");
+    return !(fz && fz[0] == '0') && getenv("KT_PAIRS_HOST") == nullptr && n <= kFusedMaxN &&
+           pair_fused_lds_bytes(it) <= 150 * 1024;
+}
+
 // Per-candidate Lanczos state: the 2x2 blocks lanczos_krylov.m:88,90 writes
 // into H at step b (column-major): D = h(cur), P = h(prev), R = qr's R.
 struct PairRun {
@@ -98,10 +107,7 @@ void run_pair_batch(kt_matrix_s* A, int C, const int64_t* ei, const int64_t* ej,
     // trace_fun_update in ONE launch (k_pair_fused), no per-step grid-wide
     // hand-offs.  KT_PAIRS_FUSED=0 keeps the batched steps below; larger n
     // keeps them too (one workgroup per candidate would sweep too many rows).
-    const char* fz = getenv("KT_PAIRS_FUSED");
-    const bool fused = !(fz && fz[0] == '0') && n <= kFusedMaxN && pair_fused_lds_bytes(it) <= 150 * 1024 &&
-                       getenv("KT_PAIRS_HOST") == nullptr;
-    if (fused) {
+    if (pairs_fused_applies(n, it)) {
         const DevCSR& M = natural_csr_ordered(A);  // every reader below is on ctx->stream
         const CsrView V{M.rowptr, M.col, M.val, (int)n, M.long_rows, M.n_long, A->long_thresh,
                         kSplitThresh, M.ck_beg, M.ck_end, M.n_chunks, M.sp_rows, M.sp_first, M.n_split};
@@ -111,8 +117,8 @@ void run_pair_batch(kt_matrix_s* A, int C, const int64_t* ei, const int64_t* ej,
         const int nnmax = 2 * it;
         int64_t big_stride = 0;
         double* big = nullptr;
-        const char* de = getenv("KT_PAIRS_DENSE_EIG");  // the dense solver needs global scratch past 2j = 56
-        if (de && de[0] == '1' && nnmax > 56) {  // G, T, d/e, eigenvalues per candidate
+        // the dense solver needs global scratch past 2j = 56: G, T, d/e, eigenvalues per candidate
+        if (pairs_dense_eig() && nnmax > 56) {
             big_stride = 2 * (int64_t)nnmax * nnmax + 6 * (int64_t)nnmax;
             ws.pair_scratch.ensure(sizeof(double) * (size_t)C * big_stride);
             big = ws.pair_scratch.as<double>();
@@ -213,8 +219,7 @@ void run_pair_batch(kt_matrix_s* A, int C, const int64_t* ei, const int64_t* ej,
         const int64_t sstride = 2 * (int64_t)nnmax * nnmax + 3 * (int64_t)nnmax;
         ws.pair_hist.ensure(sizeof(double) * (size_t)it * C * 11);
         ws.pair_state.ensure(sizeof(double) * (size_t)C * 8 + sizeof(double) * 4 * (size_t)C);
-        const char* dense_eig = getenv("KT_PAIRS_DENSE_EIG");  // only the dense solver uses the scratch
-        if (dense_eig && dense_eig[0] == '1') ws.pair_scratch.ensure(sizeof(double) * (size_t)C * sstride);
+        if (pairs_dense_eig()) ws.pair_scratch.ensure(sizeof(double) * (size_t)C * sstride);
         ws.pair_active.ensure(sizeof(int) * 2);
         ws.pair_active_host.ensure(sizeof(int) * 2);
         double* hist = ws.pair_hist.as<double>();
@@ -564,10 +569,7 @@ bool greedy_steps_device(kt_matrix_s* A, int k, int64_t Q, const std::vector<int
     const char* ge = getenv("KT_GREEDY_DEVICE");
     if (ge && ge[0] == '0') return false;
     const int64_t n = A->n, ntop = (int64_t)Ti.size();
-    const char* fz = getenv("KT_PAIRS_FUSED");
-    if (k <= 0 || n <= 130 || ntop > 4096 || ntop < k || Q > kMaxPairs || (fz && fz[0] == '0') ||
-        getenv("KT_PAIRS_HOST") || n > kFusedMaxN || pair_fused_lds_bytes(it) > 150 * 1024)
-        return false;
+    if (k <= 0 || n <= 130 || ntop > 4096 || ntop < k || Q > kMaxPairs || !pairs_fused_applies(n, it)) return false;
     for (int64_t h = 0; h < ntop; ++h)
         if (Ti[h] == Tj[h] || Ti[h] < 0 || Ti[h] >= n || Tj[h] < 0 || Tj[h] >= n) return false;
     if (A->nnz - 2 * (int64_t)(k - 1) < 2) return false;  // krylov_miobi.m:63-65 would fire: host loop

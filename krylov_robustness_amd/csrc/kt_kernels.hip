@@ -60,23 +60,17 @@ template <int P> using Geo = GeoW<P, (P >= 2) ? 2 : 1>;
 // K1: 32 B per lane from P = 16 on -- a 128-B probe row is 4 lanes, 16 rows
 // in flight per wave (K1 -4 %, profiles/r01_sweep_vec4.txt; K2 is faster
 // with 16 B per lane and keeps Geo)
-#ifndef KT_K1_VW
-#define KT_K1_VW 4
-#endif
-template <int P> using GeoK1 = GeoW<P, (P >= 16) ? (KT_K1_VW < P ? KT_K1_VW : P) : (P >= 2) ? 2 : 1>;
+constexpr int kK1VW = 4;
+template <int P> using GeoK1 = GeoW<P, (P >= 16) ? (kK1VW < P ? kK1VW : P) : (P >= 2) ? 2 : 1>;
 // y-form passes (start + step): 16 B per lane, 8 lanes per 128-B probe row.
 // 72 VGPRs = 3 workgroups of 512 per CU vs 118 VGPRs = 2 with 32 B per lane:
 // +1.4 % evals/s with two sweep lanes (profiles/r02_ab_occupancy.txt); 4 per
 // CU (64 VGPRs) is 10 % slower -- more rows in flight thrash the L2.
-#ifndef KT_KY_VW
-#define KT_KY_VW 2
-#endif
-template <int P> using GeoKY = GeoW<P, (P >= 16) ? (KT_KY_VW < P ? KT_KY_VW : P) : (P >= 2) ? 2 : 1>;
+constexpr int kKyVW = 2;
+template <int P> using GeoKY = GeoW<P, (P >= 16) ? (kKyVW < P ? kKyVW : P) : (P >= 2) ? 2 : 1>;
 // block SpMM lane width (doubles per lane) from P = 16 on
-#ifndef KT_BLK_VW
-#define KT_BLK_VW 2
-#endif
-template <int P> using GeoB = GeoW<P, (P >= 16) ? KT_BLK_VW : (P >= 2) ? 2 : 1>;
+constexpr int kBlkVW = 2;
+template <int P> using GeoB = GeoW<P, (P >= 16) ? kBlkVW : (P >= 2) ? 2 : 1>;
 
 // FLAGS bit 1: unit-weight adjacency (every stored value is 1.0, detected at
 // matrix creation): the values array is never read (4 B per nonzero instead
@@ -97,12 +91,6 @@ template <int P> using GeoB = GeoW<P, (P >= 16) ? KT_BLK_VW : (P >= 2) ? 2 : 1>;
 // FLAGS bit 6 (y-form passes): also form the Lanczos vector v_{j+1} (the
 // basis of f(A) x = ||x|| V f(T) e1) from the pass's own rows.
 enum : int { KF_NT = 1, KF_UNIT = 2, KF_MLP = 4, KF_NTY = 8, KF_SC1 = 16, KF_MU0 = 32, KF_VB = 64 };
-
-// KT_KY_DIAG (diagnostic builds of the y-form pass only, tools/ky_diag.sh; their
-// results are wrong): 1 = gathers + own row, 2 = gathers only, 3 = row streams only
-#ifndef KT_KY_DIAG
-#define KT_KY_DIAG 0
-#endif
 
 typedef unsigned int kt_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int kt_u32x2 __attribute__((ext_vector_type(2)));
@@ -536,9 +524,9 @@ __device__ __forceinline__ void ycoef_probe(int p, int P, double d0, double d1, 
 // pass, which still owes v_{m-1}.  No extra gathers: +24 n bcols bytes per
 // pass where the explicit sweep's K1 + K2 move 32 n P more.
 // ---------------------------------------------------------------------------
-template <int P, int FLAGS, class G = Geo<P>, class C = const double*>
-__device__ __forceinline__ void row_epilogue_y(int row, int p0, const double* s, C cg,
-                                               C ca, C cb, bool has_old,
+template <int P, int FLAGS, class G = Geo<P>>
+__device__ __forceinline__ void row_epilogue_y(int row, int p0, const double* s, const double* cg,
+                                               const double* ca, const double* cb, bool has_old,
                                                const double* __restrict__ X,
                                                const double* __restrict__ Yold,
                                                double* __restrict__ Out, double* d0, double* d1,
@@ -548,13 +536,6 @@ __device__ __forceinline__ void row_epilogue_y(int row, int p0, const double* s,
                                                double* __restrict__ Vn = nullptr, int bcols = 0) {
     using V = VecT<G::VEC>;
     const int64_t off = (int64_t)row * P + p0;
-#if KT_KY_DIAG == 2
-    // diagnostic build (tools/ky_diag.sh): gathers only -- no own-row read, no
-    // y_{j-1} read, no y_{j+1} store; the dots keep the gathered sums live
-#pragma unroll
-    for (int e = 0; e < G::VEC; ++e) d0[e] = fma(s[e], s[e], d0[e]);
-    return;
-#endif
     const typename V::T xi = V::load(X + off);
     if constexpr (FLAGS & KF_VB) {
         if (p0 < bcols) {
@@ -569,13 +550,6 @@ __device__ __forceinline__ void row_epilogue_y(int row, int p0, const double* s,
             }
         }
     }
-#if KT_KY_DIAG == 1
-    // diagnostic build: gathers + the own-row read (alpha's y_j . t), no
-    // y_{j-1} read and no y_{j+1} store
-#pragma unroll
-    for (int e = 0; e < G::VEC; ++e) d0[e] = fma(V::get(xi, e), s[e], d0[e]);
-    return;
-#endif
     if (!Out) {  // last pass: only alpha (X.t) is still needed
 #pragma unroll
         for (int e = 0; e < G::VEC; ++e) d0[e] = fma(V::get(xi, e), s[e], d0[e]);
@@ -738,21 +712,8 @@ __global__ __launch_bounds__(BLOCK) void k_spmm_lanczos_start(
     }
 }
 
-// KT_KY_WPE: minimum waves per SIMD the y-form pass is compiled for (register
-// budget: 8 -> <= 64 VGPRs = 4 workgroups of 512 per CU; 0 = compiler's choice)
-#ifndef KT_KY_WPE
-#define KT_KY_WPE 0
-#endif
-#ifndef KT_KY_CF_LDS
-#define KT_KY_CF_LDS 0
-#endif
-#if KT_KY_WPE > 0
-#define KT_KY_BOUNDS(B) __launch_bounds__(B, KT_KY_WPE)
-#else
-#define KT_KY_BOUNDS(B) __launch_bounds__(B)
-#endif
 template <int P, int BLOCK, int FLAGS>
-__global__ KT_KY_BOUNDS(BLOCK) void k_spmm_lanczos(
+__global__ __launch_bounds__(BLOCK) void k_spmm_lanczos(
     const int* __restrict__ row_ptr, const int* __restrict__ col, const double* __restrict__ val,
     int n, const double* __restrict__ X, const double* __restrict__ Yold, double* __restrict__ Out,
     const double* __restrict__ coef, double* __restrict__ partial,
@@ -773,16 +734,6 @@ __global__ KT_KY_BOUNDS(BLOCK) void k_spmm_lanczos(
     double d0[G::VEC], d1[G::VEC], d2[G::VEC];
 #pragma unroll
     for (int e = 0; e < G::VEC; ++e) d0[e] = d1[e] = d2[e] = 0.0;
-#if KT_KY_CF_LDS
-    // (g, a, b) read from LDS per row instead of 3 x VEC registers per lane
-    // (volatile: the compiler must not hoist them back into registers)
-    __shared__ double s_cf[3 * P];
-    for (int t = threadIdx.x; t < 3 * P; t += BLOCK) s_cf[t] = coef[t];
-    __syncthreads();
-    const volatile double* cg = s_cf + p0;
-    const volatile double* ca = s_cf + P + p0;
-    const volatile double* cb = s_cf + 2 * P + p0;
-#else
     double cg[G::VEC], ca[G::VEC], cb[G::VEC];
 #pragma unroll
     for (int e = 0; e < G::VEC; ++e) {
@@ -790,7 +741,6 @@ __global__ KT_KY_BOUNDS(BLOCK) void k_spmm_lanczos(
         ca[e] = coef[P + p0 + e];
         cb[e] = coef[2 * P + p0 + e];
     }
-#endif
 
     if ((int)blockIdx.x < long_blocks) {
         for (int li = blockIdx.x * WAVES + wave; li < n_long; li += long_blocks * WAVES) {
@@ -800,16 +750,14 @@ __global__ KT_KY_BOUNDS(BLOCK) void k_spmm_lanczos(
             double s[G::VEC];
 #pragma unroll
             for (int e = 0; e < G::VEC; ++e) s[e] = 0.0;
-#if KT_KY_DIAG != 3
             gather_row<P, FLAGS, G>(beg + grp, end, G::GPW, p0, col, val, X, s);
-#endif
 #pragma unroll
             for (int o = G::LPR; o < 64; o <<= 1)
 #pragma unroll
                 for (int e = 0; e < G::VEC; ++e) s[e] += kt::shfl_xor(s[e], o);
             if (grp == 0)
-                row_epilogue_y<P, FLAGS, G, decltype(cg)>(row, p0, s, cg, ca, cb, has_old, X, Yold, Out, d0, d1, d2,
-                                           orsrc, Vc, Vo, Vn, bcols);
+                row_epilogue_y<P, FLAGS, G>(row, p0, s, cg, ca, cb, has_old, X, Yold, Out, d0, d1, d2,
+                                            orsrc, Vc, Vo, Vn, bcols);
         }
     } else {
         const int sb = blockIdx.x - long_blocks;
@@ -821,11 +769,9 @@ __global__ KT_KY_BOUNDS(BLOCK) void k_spmm_lanczos(
             double s[G::VEC];
 #pragma unroll
             for (int e = 0; e < G::VEC; ++e) s[e] = 0.0;
-#if KT_KY_DIAG != 3  // diagnostic build 3: the row streams alone (no column / gather loads)
             gather_row<P, FLAGS, G>(beg, end, 1, p0, col, val, X, s);
-#endif
-            row_epilogue_y<P, FLAGS, G, decltype(cg)>(row, p0, s, cg, ca, cb, has_old, X, Yold, Out, d0, d1, d2,
-                                           orsrc, Vc, Vo, Vn, bcols);
+            row_epilogue_y<P, FLAGS, G>(row, p0, s, cg, ca, cb, has_old, X, Yold, Out, d0, d1, d2,
+                                        orsrc, Vc, Vo, Vn, bcols);
         }
     }
 
@@ -1516,10 +1462,7 @@ __device__ __forceinline__ void expmv_row_update(int row, int p0, const double* 
 // is one block's, its gather chain degree / (16 WAVES) deep).  8 waves were
 // measured slower than 4 on config 1 (trace_exp 18.1 vs 16.1 ms,
 // profiles/r02_expmv_waves.txt): the hub chains are not the term's limit.
-#ifndef KT_EXPMV_WAVES
-#define KT_EXPMV_WAVES 4
-#endif
-constexpr int kExpmvWaves = KT_EXPMV_WAVES;
+constexpr int kExpmvWaves = 4;
 // grids above this many workgroups take the SPLIT term kernel (config 1: 340
 // workgroups, fused; n = 1M: 31k, split)
 constexpr int kExpmvSplitBlocks = 1024;
@@ -1742,7 +1685,7 @@ __global__ __launch_bounds__(64 * kExpmvRowsWaves) void k_expmv_rows(
     int nc, int ld, double mu, double coef, int k, const double* __restrict__ bin,
     double* __restrict__ bout, double* __restrict__ F, ExpmvState* st, double tol, int* hflag, int stage) {
     constexpr int WAVES = kExpmvRowsWaves;
-    constexpr int VW = 4;                                          // the fused kernel's waves per long row
+    constexpr int VW = kExpmvWaves;                                // the fused kernel's waves per long row
     using G = GeoW<P, (P >= 2) ? 2 : 1>;                          // short rows
     using GL = GeoW<P, (P >= 4) ? 4 : (P >= 2) ? 2 : 1>;          // medium / long rows
     constexpr bool MU0 = (FLAGS & KF_MU0) != 0;
@@ -2465,18 +2408,16 @@ hipError_t launch_expmv_slot_check(void* state, int k, double tol, hipStream_t s
 // form: 0 fused, 1 split (a workgroup per long row / 4 medium rows / 32 short
 // rows), 2 row-blocked split (k_expmv_rows, resident workgroups)
 static int expmv_rows_grid(int n_tasks_hint) {
-    static int per_cu = 0, cus = 0;
-    if (!per_cu) {
-        int dev = 0;
+    // resident workgroups of the device, found once (one thread-safe static)
+    static const int resident = [] {
+        int dev = 0, cus = 0, occ = 0;
         (void)hipGetDevice(&dev);
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        int occ = 0;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_expmv_rows<16, KF_UNIT | KF_MU0, true>,
                                                            64 * kExpmvRowsWaves, 0);
-        per_cu = occ > 0 ? occ : 2;
-        if (cus <= 0) cus = 256;
-    }
-    int g = per_cu * cus;
+        return (occ > 0 ? occ : 2) * (cus > 0 ? cus : 256);
+    }();
+    int g = resident;
     if (g > n_tasks_hint) g = n_tasks_hint;
     return g < 1 ? 1 : g;
 }

@@ -49,6 +49,9 @@ constexpr int kMedThresh = 16;     // expmv terms: rows longer than this get a w
 // k_pair_fused); vec: C x 3 x n x 2 doubles; big: C x big_stride doubles of
 // eigen scratch, needed only when 2 it > 56 (else may be null); state: C x 8.
 size_t pair_fused_lds_bytes(int it);
+// KT_PAIRS_DENSE_EIG=1 (read per call): the dense projected eigensolvers
+// instead of block Sturm counts, in every candidate kernel
+bool pairs_dense_eig();
 hipError_t launch_pair_fused(int C, int n, int64_t nnz, const CsrView& A, bool unit, const int* ii,
                              const int* jj, const double* B, int it, int fun, double tol, double* vec,
                              double* big, int64_t big_stride, double* state, hipStream_t st);

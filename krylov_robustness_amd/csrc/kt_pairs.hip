@@ -28,6 +28,7 @@
 #include <cstdlib>
 
 #include "kt_launch.h"
+#include "kt_wave.h"
 
 namespace kt {
 
@@ -470,119 +471,7 @@ __global__ void k_pair_eig(int C, int j, int it, int fun, double tol,
 
 // ---- one workgroup per candidate (2j <= 56): wave 0 solves the updated
 // projection T, wave 1 the plain one G, concurrently; both live in LDS ----
-// The xor butterfly v += v[lane ^ o], o = 32, 16, ..., 1, in every lane.
-// KT_WAVE_DPP=1 (default) moves the partners without the LDS crossbar
-// (__shfl_xor compiles to two ds_bpermute_b32 per double and step, ~400 of
-// them in k_pair_reg, each an LDS round trip): o = 32, 16 by gfx950's
-// v_permlane32/16_swap (the swap hands every lane its partner half: the sum
-// lo + hi is own + partner up to the order of the operands, which fp64
-// addition ignores), o = 8 by DPP row_ror:8 (= lane ^ 8 within a row of 16),
-// o = 4 by row_ror:4 (lane (i - 4) mod 16 holds the same value as lane i ^ 4
-// once the o = 8 step made lanes i and i ^ 8 equal), o = 2, 1 by quad_perm.
-// Every lane adds the same pairs as the shuffle form: bit-identical sums.
-// Wave-uniform control flow only (every call site: the DPP moves read the
-// other lanes' registers).
-#ifndef KT_WAVE_DPP
-#define KT_WAVE_DPP 1
-#endif
-template <int CTRL>
-__device__ __forceinline__ double mov_dpp_d(double v) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-template <bool B32>
-__device__ __forceinline__ double swap_sum_d(double v) {
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
-    const auto rl = B32 ? __builtin_amdgcn_permlane32_swap(lo, lo, false, false)
-                        : __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto rh = B32 ? __builtin_amdgcn_permlane32_swap(hi, hi, false, false)
-                        : __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    const double x0 = __longlong_as_double(((long long)rh[0] << 32) | (unsigned int)rl[0]);
-    const double x1 = __longlong_as_double(((long long)rh[1] << 32) | (unsigned int)rl[1]);
-    return x0 + x1;
-}
-// min / max over the wave (exact and commutative: any pairing gives the
-// shuffle butterfly's value), same moves as wave_sum64
-template <bool MAX, bool B32>
-__device__ __forceinline__ double swap_mm_d(double v) {
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
-    const auto rl = B32 ? __builtin_amdgcn_permlane32_swap(lo, lo, false, false)
-                        : __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto rh = B32 ? __builtin_amdgcn_permlane32_swap(hi, hi, false, false)
-                        : __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    const double x0 = __longlong_as_double(((long long)rh[0] << 32) | (unsigned int)rl[0]);
-    const double x1 = __longlong_as_double(((long long)rh[1] << 32) | (unsigned int)rl[1]);
-    return MAX ? fmax(x0, x1) : fmin(x0, x1);
-}
-template <bool MAX>
-__device__ __forceinline__ double wave_minmax64(double v) {
-#if KT_WAVE_DPP
-    v = swap_mm_d<MAX, true>(v);
-    v = swap_mm_d<MAX, false>(v);
-    v = MAX ? fmax(v, mov_dpp_d<0x128>(v)) : fmin(v, mov_dpp_d<0x128>(v));
-    v = MAX ? fmax(v, mov_dpp_d<0x124>(v)) : fmin(v, mov_dpp_d<0x124>(v));
-    v = MAX ? fmax(v, mov_dpp_d<0x4E>(v)) : fmin(v, mov_dpp_d<0x4E>(v));
-    v = MAX ? fmax(v, mov_dpp_d<0xB1>(v)) : fmin(v, mov_dpp_d<0xB1>(v));
-#else
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = MAX ? fmax(v, __shfl_xor(v, o, 64)) : fmin(v, __shfl_xor(v, o, 64));
-#endif
-    return v;
-}
-// min over the aligned group of g lanes (g a power of two <= 64, wave-uniform)
-__device__ __forceinline__ int group_min_i(int v, int g) {
-#if KT_WAVE_DPP
-    if (g > 1) v = min(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, false));  // lane ^ 1
-    if (g > 2) v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, false));  // lane ^ 2
-    if (g > 4) v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, false)); // 7 - i: the other quad
-    if (g > 8) v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, false)); // 15 - i: the other 8
-    if (g > 16) {
-        const auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-        v = min((int)r[0], (int)r[1]);
-    }
-    if (g > 32) {
-        const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-        v = min((int)r[0], (int)r[1]);
-    }
-#else
-    for (int o = 1; o < g; o <<= 1) v = min(v, __shfl_xor(v, o, 64));
-#endif
-    return v;
-}
-__device__ __forceinline__ double wave_sum64(double v) {
-#if KT_WAVE_DPP
-    v = swap_sum_d<true>(v);
-    v = swap_sum_d<false>(v);
-    v += mov_dpp_d<0x128>(v);  // row_ror:8
-    v += mov_dpp_d<0x124>(v);  // row_ror:4
-    v += mov_dpp_d<0x4E>(v);   // quad_perm [2,3,0,1]
-    v += mov_dpp_d<0xB1>(v);   // quad_perm [1,0,3,2]
-#else
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-#endif
-    return v;
-}
-
-// LDS hand-off between the lanes of ONE wave (the two waves of the block run
-// data-dependent control flow, so no workgroup barrier inside the solvers)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// lane l's double, broadcast to the wave (l uniform): two v_readlane, no LDS
-__device__ __forceinline__ double readlane_d(double v, int l) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)b, l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
+// (wave_sum64, wave_minmax64, group_min_i, readlane_d, wave_sync: kt_wave.h)
 
 // Householder tridiagonalisation (dsytd2, lower) of the symmetric n x n LDS
 // matrix A (row stride n, n <= 64, destroyed) by one wave: lane i owns
@@ -867,10 +756,7 @@ __global__ __launch_bounds__(128 * W) void k_pair_eig_wave(int C, int j, int it,
 // launches per step over all candidates.  The candidate's vectors live in
 // its own slice of `vec` ([C][3][n][2], L2-resident for small n).
 // ---------------------------------------------------------------------------
-#ifndef KT_FUSED_THREADS
-#define KT_FUSED_THREADS 512
-#endif
-constexpr int kFusedThreads = KT_FUSED_THREADS;
+constexpr int kFusedThreads = 512;
 constexpr int kFusedWaves = kFusedThreads / 64;
 constexpr int kFusedMaxNN = 56;  // 2j at which the eigenproblems leave LDS
 
@@ -1343,37 +1229,28 @@ __device__ __forceinline__ int group_lanes(int ne) {
     return g;
 }
 
-#ifndef KT_BLK_NEWTON
-#define KT_BLK_NEWTON 1
-#endif
 // Newton's last step is taken and the run ends once the step is below
-// KT_BLK_NEWTON_ACCEPT atol (2^20 atol ~ 5e-10 of the spectral radius: the
+// kBlkNewtonAccept atol (2^20 atol ~ 5e-10 of the spectral radius: the
 // step's quadratic error is far below atol), then certified by the counts
 // at x -+ 8 atol as before -- a lane that fails goes on bisecting.  One
 // Newton count fewer per eigenvalue than at 64 atol: config 5 -1 %
 // (profiles/r02_greedy_newton_accept.txt)
-#ifndef KT_BLK_NEWTON_ACCEPT
-#define KT_BLK_NEWTON_ACCEPT 1048576
-#endif
+constexpr double kBlkNewtonAccept = 1048576.0;
 // shifts per lane per multisection round.  The eigenvalue phase is bound by
 // FP64 issue (a wave64 FMA takes 4 cycles; 2 waves per SIMD), not latency, so
 // fewer shifts with more rounds does less work: 1 beats 4 by 4 % end to end
 // on config 5 (profiles/r02_greedy_blk_ms.txt)
-#ifndef KT_BLK_MS
-#define KT_BLK_MS 1
-#endif
+constexpr int kBlkMS = 1;
 // Waves per projection for the per-step eigenvalues (both the fused and the
-// register kernel, so they solve identically): KT_XM_WAVES_SMALL while each
+// register kernel, so they solve identically): kXmWavesSmall while each
 // wave still holds <= 16 eigenvalues (g >= 4 lanes each: the Newton path),
 // else half the workgroup.  Fewer waves issue fewer FP64 operations in total;
 // the others wait at the barrier (2 waves: config 5 -2-3 %,
 // profiles/r02_greedy_xm_waves.txt)
-#ifndef KT_XM_WAVES_SMALL
-#define KT_XM_WAVES_SMALL 2
-#endif
+constexpr int kXmWavesSmall = 2;
 __device__ __forceinline__ int xm_waves(int nn) {
     constexpr int half = kFusedWaves / 2;
-    constexpr int small = KT_XM_WAVES_SMALL < half ? KT_XM_WAVES_SMALL : half;
+    constexpr int small = kXmWavesSmall < half ? kXmWavesSmall : half;
     return nn <= 16 * small ? small : half;
 }
 
@@ -1383,11 +1260,10 @@ __device__ __forceinline__ int xm_waves(int nn) {
 // every bracket is span/4096 wide a safeguarded Newton iteration
 // on det(M - xI) (block_count_newton; a step leaving the count bracket is a
 // bisection) converges in ~4 steps, and is accepted once its step is below
-// KT_BLK_NEWTON_ACCEPT atol AND the counts at x -+ 8 atol bracket lambda_k (certified to
+// kBlkNewtonAccept atol AND the counts at x -+ 8 atol bracket lambda_k (certified to
 // 8 atol = 3.5e-15 of the spectral radius).  Lanes whose Newton run is not
 // certified (~1 % on the greedy projections, tests/test_block_sturm.py)
-// continue the multisection to 2 ulp of the spectral radius (as before:
-// KT_BLK_NEWTON=0 builds that alone).  Returns lambda_{k0 + lane / g} in
+// continue the multisection to 2 ulp of the spectral radius.  Returns lambda_{k0 + lane / g} in
 // every lane of group lane / g < ne.
 // m0 (optional): (a, b, c) of the first diagonal block in place of B[0]'s --
 // the updated projection T differs from G only there (T = G + Cm)
@@ -1453,56 +1329,54 @@ __device__ __forceinline__ double wave_multisect_blk(int j, const Blk2* B, int k
         }
     };
     int round = 0;
-#if KT_BLK_NEWTON
     // Newton pays where a wave holds <= 16 eigenvalues (g >= 4): with more, one
     // uncertified lane in the wave sends all of them back to the multisection
     // (measured: 2j = 80 at 4 waves per projection is 10 % slower with it)
     if (g >= 4) {
-    // multisection until every bracket is within span / 4096 (ceil(12 /
-    // log2(g MS + 1)) rounds: 3 at g = 16, MS = 1), where Newton converges in
-    // ~4 steps
-    const double narrow = (hi - lo) * (1.0 / 4096.0);
-    for (; round < 64; ++round) {
-        if (!done && !(b - a > atol)) done = true;
-        if (__ballot(!done && b - a > narrow) == 0ull) break;
-        ms_round();
-    }
-    bool newton = !done, conv = false;
-    double x = 0.5 * (a + b);
-    for (int it = 0; it < 8; ++it) {
-        if (__ballot(newton && !conv) == 0ull) break;
-        if (newton && !conv) {
-            int cnt;
-            double S;
-            block_count_newton<HAS_M0>(j, B, x, pivmin, eps, cnt, S, m0);
-            if (cnt > k) b = x;
-            else a = x;
-            const double xn = x - 1.0 / S;  // S = 0 or inf: xn is not finite / = x
-            const bool inb = xn >= a && xn <= b;
-            if (fabs(xn - x) <= (double)KT_BLK_NEWTON_ACCEPT * atol || !(b - a > atol)) {
-                conv = true;
-                if (inb) x = xn;
-            } else {
-                x = inb ? xn : 0.5 * (a + b);
+        // multisection until every bracket is within span / 4096 (ceil(12 /
+        // log2(g MS + 1)) rounds: 3 at g = 16, MS = 1), where Newton converges in
+        // ~4 steps
+        const double narrow = (hi - lo) * (1.0 / 4096.0);
+        for (; round < 64; ++round) {
+            if (!done && !(b - a > atol)) done = true;
+            if (__ballot(!done && b - a > narrow) == 0ull) break;
+            ms_round();
+        }
+        bool newton = !done, conv = false;
+        double x = 0.5 * (a + b);
+        for (int it = 0; it < 8; ++it) {
+            if (__ballot(newton && !conv) == 0ull) break;
+            if (newton && !conv) {
+                int cnt;
+                double S;
+                block_count_newton<HAS_M0>(j, B, x, pivmin, eps, cnt, S, m0);
+                if (cnt > k) b = x;
+                else a = x;
+                const double xn = x - 1.0 / S;  // S = 0 or inf: xn is not finite / = x
+                const bool inb = xn >= a && xn <= b;
+                if (fabs(xn - x) <= kBlkNewtonAccept * atol || !(b - a > atol)) {
+                    conv = true;
+                    if (inb) x = xn;
+                } else {
+                    x = inb ? xn : 0.5 * (a + b);
+                }
+            }
+        }
+        if (__ballot(newton && conv) != 0ull) {  // certify: #eig < x - 8 atol <= k < #eig < x + 8 atol
+            int cnt[2] = {0, 0};
+            if (newton && conv) {
+                const double xs[2] = {x - 8.0 * atol, x + 8.0 * atol};
+                block_count_ms<2, HAS_M0>(j, B, xs, pivmin, eps, cnt, m0);
+                if (cnt[0] <= k && cnt[1] > k) {
+                    done = true;
+                    a = b = x;
+                } else {  // keep the tighter count bracket for the multisection
+                    if (cnt[0] <= k) a = fmax(a, xs[0]);
+                    if (cnt[1] > k) b = fmin(b, xs[1]);
+                }
             }
         }
     }
-    if (__ballot(newton && conv) != 0ull) {  // certify: #eig < x - 8 atol <= k < #eig < x + 8 atol
-        int cnt[2] = {0, 0};
-        if (newton && conv) {
-            const double xs[2] = {x - 8.0 * atol, x + 8.0 * atol};
-            block_count_ms<2, HAS_M0>(j, B, xs, pivmin, eps, cnt, m0);
-            if (cnt[0] <= k && cnt[1] > k) {
-                done = true;
-                a = b = x;
-            } else {  // keep the tighter count bracket for the multisection
-                if (cnt[0] <= k) a = fmax(a, xs[0]);
-                if (cnt[1] > k) b = fmin(b, xs[1]);
-            }
-        }
-    }
-    }
-#endif
     for (; round < 64; ++round) {
         if (!done && !(b - a > atol)) done = true;
         if (__ballot(!done) == 0ull) break;
@@ -1551,7 +1425,7 @@ __device__ double fused_xm_blk(int j, int fun, const double* rec /* [j][11] */, 
     const int ne = mat < 2 ? min(per, nn - k0) : 0;
     for (int e0 = 0; e0 < ne; e0 += 64) {  // more than 64 eigenvalues per wave: 64 at a time
         const int cnt = min(64, ne - e0);
-        const double lam = wave_multisect_blk<KT_BLK_MS>(j, blk + mat * j, k0 + e0, cnt);
+        const double lam = wave_multisect_blk<kBlkMS>(j, blk + mat * j, k0 + e0, cnt);
         const int g = group_lanes(cnt);
         if (lane % g == 0 && lane / g < cnt) ev[mat * nn + k0 + e0 + lane / g] = lam;
     }
@@ -1630,15 +1504,10 @@ __global__ __launch_bounds__(kFusedThreads) void k_pair_fused(
             iter = -j;
             break;
         }
-#ifdef KT_FUSED_NOEIG  // diagnostic build: vector work only (never stops early)
-        xm = (double)j;
-        (void)eigsm;
-#else
         if (blk_eig)
             xm = fused_xm_blk(j, fun, rec, cm, reinterpret_cast<Blk2*>(eigsm), eigsm + 14 * (size_t)it);
         else
             xm = fused_xm(j, fun, rec, cm, eigsm, mybig);
-#endif
         FPROF(7);
         const double* hj = rec + 11 * (j - 1);
         lucky = sqrt(hj[8] * hj[8] + hj[9] * hj[9] + hj[10] * hj[10]) < 1e-8;  // :91-93
@@ -1919,23 +1788,15 @@ __host__ __device__ inline RegLds reg_lds_layout(int n, int64_t nnz, int it, boo
 // Xm of step j from the persistent G blocks (T = G but for T's first
 // diagonal block t0): fused_xm_blk's arithmetic without rebuilding the
 // blocks every step.  Waves 0..W-1 solve T, W..2W-1 G.
-// Inlined into k_pair_reg (KT_REG_XM_INLINE=0 builds it as a called function:
-// each call then saves callee-saved registers to scratch)
-#ifndef KT_REG_XM_INLINE
-#define KT_REG_XM_INLINE 1
-#endif
+// Inlined into k_pair_reg (as a called function each call saves callee-saved
+// registers to scratch).
 // help(): called by every wave once its share of the eigenvalues is done,
 // before the phase's first barrier (k_pair_reg: the next step's row sums)
 struct NoHelp {
     __device__ void operator()() const {}
 };
 template <class Help = NoHelp>
-#if KT_REG_XM_INLINE
-__device__ __forceinline__
-#else
-__device__ __noinline__
-#endif
-double reg_xm_blk(int j, int fun, const Blk2* gblk, const double* t0, double* ev, const Help& help = Help()) {
+__device__ __forceinline__ double reg_xm_blk(int j, int fun, const Blk2* gblk, const double* t0, double* ev, const Help& help = Help()) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int nn = 2 * j;
     const int W = xm_waves(nn);  // waves per projection; the rest wait at the barrier
@@ -1945,8 +1806,8 @@ double reg_xm_blk(int j, int fun, const Blk2* gblk, const double* t0, double* ev
     const int ne = mat < 2 ? min(per, nn - k0) : 0;
     for (int e0 = 0; e0 < ne; e0 += 64) {
         const int cnt = min(64, ne - e0);
-        const double lam = mat == 0 ? wave_multisect_blk<KT_BLK_MS, true>(j, gblk, k0 + e0, cnt, t0)
-                                    : wave_multisect_blk<KT_BLK_MS, false>(j, gblk, k0 + e0, cnt);
+        const double lam = mat == 0 ? wave_multisect_blk<kBlkMS, true>(j, gblk, k0 + e0, cnt, t0)
+                                    : wave_multisect_blk<kBlkMS, false>(j, gblk, k0 + e0, cnt);
         const int g = group_lanes(cnt);
         if (lane % g == 0 && lane / g < cnt) ev[mat * nn + k0 + e0 + lane / g] = lam;
     }
@@ -1975,22 +1836,6 @@ double reg_xm_blk(int j, int fun, const Blk2* gblk, const double* t0, double* ev
 #ifndef KT_REG_SPEC_DYN
 #define KT_REG_SPEC_DYN 1
 #endif
-
-// KT_REG_ZROW=0: unused chunk slots repeat the row's last column (round 5)
-#ifndef KT_REG_ZROW
-#define KT_REG_ZROW 1
-#endif
-
-// One gathered row (2 doubles) of the LDS block X; the KT_REG_DIAG=1
-// diagnostic build replaces it by a register value (no gather; its results
-// are wrong by construction, only its clocks mean anything)
-__device__ __forceinline__ double2 reg_gather(const double* X, int c) {
-#if defined(KT_REG_DIAG) && KT_REG_DIAG >= 1
-    return make_double2((double)c, 1.0);
-#else
-    return *reinterpret_cast<const double2*>(X + 2 * c);
-#endif
-}
 
 // CSR: 0 = CSR in global memory, 1 = row pointers + u16 columns in LDS, 2 = and
 // the weights.  A template argument, so every CSR access has a known address
@@ -2083,8 +1928,11 @@ __global__ __launch_bounds__(kFusedThreads) void k_pair_reg(int C, int n, int nn
     FPROF(0);
     double x0 = 0.0, x1 = 0.0, xm = 0.0;
     int iter = it, lucky = 0;
-    // one row's sum of W = A C, in CSR order (the owners' loop below, for the
-    // rows waves 4-7 sum ahead into ws)
+    // One row's sum of W = A C, in CSR order, for the rows summed ahead into ws
+    // (spec_rows).  The owners' loop below holds the SAME loop inline and the
+    // two must agree bit for bit: calling row_sum there instead compiles to a
+    // different block layout, measured 0.5-0.7 % slower on config 5
+    // (profiles/variant_prune/).
     auto row_sum = [&](int r, double& s0, double& s1) {
         const int rb = rp[r], re = rp[r + 1];
         if (M.unit) {
@@ -2093,11 +1941,11 @@ __global__ __launch_bounds__(kFusedThreads) void k_pair_reg(int C, int n, int nn
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int c0 = col(min(k0 + u, re - 1));
-                    cc[u] = (KT_REG_ZROW && k0 + u >= re) ? n : c0;
+                    cc[u] = (k0 + u >= re) ? n : c0;
                 }
                 double2 v[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) v[u] = reg_gather(X, cc[u]);
+                for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const double2*>(X + 2 * cc[u]);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const double a = (k0 + u < re) ? 1.0 : 0.0;
@@ -2113,12 +1961,12 @@ __global__ __launch_bounds__(kFusedThreads) void k_pair_reg(int C, int n, int nn
                 for (int u = 0; u < 4; ++u) {
                     const int k = min(k0 + u, re - 1);
                     const int c0 = col(k);
-                    cc[u] = (KT_REG_ZROW && k0 + u >= re) ? n : c0;
+                    cc[u] = (k0 + u >= re) ? n : c0;
                     a[u] = va[k];
                 }
                 double2 v[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) v[u] = reg_gather(X, cc[u]);
+                for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const double2*>(X + 2 * cc[u]);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const double w = (k0 + u < re) ? a[u] : 0.0;
@@ -2128,85 +1976,10 @@ __global__ __launch_bounds__(kFusedThreads) void k_pair_reg(int C, int n, int nn
             }
         }
     };
-    bool have_spec = false;  // this step's W = A C already in ws / wl (formed by waves 4-7)
-    for (int j = 1; j <= it; ++j) {
-        if (have_spec) {
-            // the sums waves 4-7 formed during the previous step's eigenvalues
-#pragma unroll
-            for (int q = 0; q < R; ++q) {
-                const int r = tid + q * kFusedThreads;
-                Cv[q] = r < n ? *reinterpret_cast<const double2*>(X + 2 * r) : make_double2(0.0, 0.0);
-                const int ls = (nl > 0 && r < n) ? slot[r] : -1;
-                W[q] = r >= n ? make_double2(0.0, 0.0)
-                     : ls >= 0 ? make_double2(wl[2 * ls], wl[2 * ls + 1])
-                               : *reinterpret_cast<const double2*>(ws + 2 * r);
-            }
-        } else {
-        // W = A C   (lanczos_krylov.m:81): short rows by their owner, gathers from LDS
-#pragma unroll
-        for (int q = 0; q < R; ++q) {
-            const int r = tid + q * kFusedThreads;
-            Cv[q] = r < n ? *reinterpret_cast<const double2*>(X + 2 * r) : make_double2(0.0, 0.0);
-            double s0 = 0.0, s1 = 0.0;
-#if defined(KT_REG_DIAG) && KT_REG_DIAG >= 2
-            if (false) {  // diagnostic: no row sums at all (the phase's fixed cost)
-#else
-            if (r < n && (nl == 0 || slot[r] < 0)) {
-#endif
-                const int rb = rp[r], re = rp[r + 1];
-                // four nonzeros per round; the indices are clamped into the row
-                // (a masked weight drops the repeats) so that every load is
-                // unconditional: the four column reads issue together, then the
-                // four gathers -- predicated loads compiled to one branch and
-                // one LDS round trip EACH (the SpMM took ~13 us per Lanczos step).
-                // A slot past the row's end gathers the zero row n instead of
-                // repeating the last column: every such lane of the wave reads
-                // one address (an LDS broadcast, not one more random access
-                // in the instruction's bank conflicts); x + 1 * 0 = x + 0 * v.
-                if (M.unit) {
-                    for (int k0 = rb; k0 < re; k0 += 4) {
-                        int cc[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const int c0 = col(min(k0 + u, re - 1));
-                            cc[u] = (KT_REG_ZROW && k0 + u >= re) ? n : c0;
-                        }
-                        double2 v[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) v[u] = reg_gather(X, cc[u]);
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const double a = (k0 + u < re) ? 1.0 : 0.0;
-                            s0 = fma(a, v[u].x, s0);
-                            s1 = fma(a, v[u].y, s1);
-                        }
-                    }
-                } else {
-                    for (int k0 = rb; k0 < re; k0 += 4) {
-                        int cc[4];
-                        double a[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const int k = min(k0 + u, re - 1);
-                            const int c0 = col(k);
-                            cc[u] = (KT_REG_ZROW && k0 + u >= re) ? n : c0;
-                            a[u] = va[k];
-                        }
-                        double2 v[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) v[u] = reg_gather(X, cc[u]);
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const double w = (k0 + u < re) ? a[u] : 0.0;
-                            s0 = fma(w, v[u].x, s0);
-                            s1 = fma(w, v[u].y, s1);
-                        }
-                    }
-                }
-            }
-            W[q] = make_double2(s0, s1);
-        }
-        for (int li = wave; li < nl; li += kFusedWaves) {
+    // the long rows first, first + stride, ... of the wave list, one wave per
+    // row, into wl (wave-uniform: first and stride are per wave)
+    auto long_rows_sum = [&](int first, int stride) {
+        for (int li = first; li < nl; li += stride) {
             const int r = M.long_rows[li];
             const int b = rp[r], e = rp[r + 1];
             double s0 = 0.0, s1 = 0.0;
@@ -2224,15 +1997,91 @@ __global__ __launch_bounds__(kFusedThreads) void k_pair_reg(int C, int n, int nn
                 wl[2 * li + 1] = s1;
             }
         }
-        if (nl > 0) {
-            __syncthreads();
+    };
+    bool have_spec = false;  // this step's W = A C already in ws / wl (formed by waves 4-7)
+    for (int j = 1; j <= it; ++j) {
+        if (have_spec) {
+            // the sums waves 4-7 formed during the previous step's eigenvalues
 #pragma unroll
             for (int q = 0; q < R; ++q) {
                 const int r = tid + q * kFusedThreads;
-                const int ls = r < n ? slot[r] : -1;
-                if (ls >= 0) W[q] = make_double2(wl[2 * ls], wl[2 * ls + 1]);
+                Cv[q] = r < n ? *reinterpret_cast<const double2*>(X + 2 * r) : make_double2(0.0, 0.0);
+                const int ls = (nl > 0 && r < n) ? slot[r] : -1;
+                W[q] = r >= n ? make_double2(0.0, 0.0)
+                     : ls >= 0 ? make_double2(wl[2 * ls], wl[2 * ls + 1])
+                               : *reinterpret_cast<const double2*>(ws + 2 * r);
             }
-        }
+        } else {
+            // W = A C   (lanczos_krylov.m:81): short rows by their owner, gathers from LDS
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const int r = tid + q * kFusedThreads;
+                Cv[q] = r < n ? *reinterpret_cast<const double2*>(X + 2 * r) : make_double2(0.0, 0.0);
+                double s0 = 0.0, s1 = 0.0;
+                if (r < n && (nl == 0 || slot[r] < 0)) {
+                    const int rb = rp[r], re = rp[r + 1];
+                    // four nonzeros per round; the indices are clamped into the row
+                    // (a masked weight drops the repeats) so that every load is
+                    // unconditional: the four column reads issue together, then the
+                    // four gathers -- predicated loads compiled to one branch and
+                    // one LDS round trip EACH (the SpMM took ~13 us per Lanczos step).
+                    // A slot past the row's end gathers the zero row n instead of
+                    // repeating the last column: every such lane of the wave reads
+                    // one address (an LDS broadcast, not one more random access
+                    // in the instruction's bank conflicts); x + 1 * 0 = x + 0 * v.
+                    if (M.unit) {
+                        for (int k0 = rb; k0 < re; k0 += 4) {
+                            int cc[4];
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const int c0 = col(min(k0 + u, re - 1));
+                                cc[u] = (k0 + u >= re) ? n : c0;
+                            }
+                            double2 v[4];
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const double2*>(X + 2 * cc[u]);
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const double a = (k0 + u < re) ? 1.0 : 0.0;
+                                s0 = fma(a, v[u].x, s0);
+                                s1 = fma(a, v[u].y, s1);
+                            }
+                        }
+                    } else {
+                        for (int k0 = rb; k0 < re; k0 += 4) {
+                            int cc[4];
+                            double a[4];
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const int k = min(k0 + u, re - 1);
+                                const int c0 = col(k);
+                                cc[u] = (k0 + u >= re) ? n : c0;
+                                a[u] = va[k];
+                            }
+                            double2 v[4];
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const double2*>(X + 2 * cc[u]);
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) {
+                                const double w = (k0 + u < re) ? a[u] : 0.0;
+                                s0 = fma(w, v[u].x, s0);
+                                s1 = fma(w, v[u].y, s1);
+                            }
+                        }
+                    }
+                }
+                W[q] = make_double2(s0, s1);
+            }
+            long_rows_sum(wave, kFusedWaves);
+            if (nl > 0) {
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < R; ++q) {
+                    const int r = tid + q * kFusedThreads;
+                    const int ls = r < n ? slot[r] : -1;
+                    if (ls >= 0) W[q] = make_double2(wl[2 * ls], wl[2 * ls + 1]);
+                }
+            }
         }  // !have_spec
         FPROF(1);
         // X is overwritten by Q in sweep E: every SpMM read is behind the sweeps' barriers
@@ -2306,37 +2155,11 @@ __global__ __launch_bounds__(kFusedThreads) void k_pair_reg(int C, int n, int nn
                     }
                 }
             }
-            for (int li = wave - kFusedWaves / 2; li < nl; li += kFusedWaves / 2) {
-                const int r = M.long_rows[li];
-                const int b = rp[r], e = rp[r + 1];
-                double s0 = 0.0, s1 = 0.0;
-                for (int k = b + lane; k < e; k += 64) {
-                    const int cc = col(k);
-                    const double a = M.unit ? 1.0 : va[k];
-                    const double2 v = *reinterpret_cast<const double2*>(X + 2 * cc);
-                    s0 = fma(a, v.x, s0);
-                    s1 = fma(a, v.y, s1);
-                }
-                s0 = wave_sum64(s0);
-                s1 = wave_sum64(s1);
-                if (lane == 0) {
-                    wl[2 * li] = s0;
-                    wl[2 * li + 1] = s1;
-                }
-            }
+            long_rows_sum(wave - kFusedWaves / 2, kFusedWaves / 2);
         }
-#ifdef KT_FUSED_NOEIG
-        spec_rows();
-        __syncthreads();
-        xm = (double)j;
-#else
         xm = reg_xm_blk(j, fun, gblk, t0, ev, spec_rows);  // its first barrier: ws / wl complete
-#endif
         FPROF(7);
         lucky = sqrt(o.beta1 * o.beta1 + o.r12 * o.r12 + o.beta2 * o.beta2) < 1e-8;  // :91-93
-#ifdef KT_FUSED_NOEIG
-        lucky = 0;  // diagnostic builds run exactly `it` steps
-#endif
         bool stop = false;
         if (j <= 2) {  // :104-118, lag d = 2
             if (j == 1) x0 = xm;
@@ -2482,75 +2305,94 @@ __global__ __launch_bounds__(1024) void k_greedy_edit(int C, const double* __res
     }
 }
 
-// Rows per thread of k_pair_reg: 2, 4, then exact from 6 (one row more costs
-// ~12 VGPRs: at R = 8 the kernel spills 6-18 VGPRs to scratch at 2 waves per
-// SIMD, R = 7 and below do not -- India, n = 3,228, takes R = 7).
-// KT_REG_R_POW2=1 builds the round-5 choice (2, 4, 8) for A/Bs.
-#ifndef KT_REG_R_POW2
-#define KT_REG_R_POW2 0
-#endif
-static int reg_rows(int n) {
-    const int rows = (n + kFusedThreads - 1) / kFusedThreads;
-    if (KT_REG_R_POW2) return rows <= 2 ? 2 : rows <= 4 ? 4 : 8;
-    return rows <= 2 ? 2 : rows <= 4 ? 4 : rows <= 6 ? 6 : rows;
+// KT_PAIRS_DENSE_EIG=1: the dense tridiagonalisation + multisection in LDS
+// (and the one-thread solver past 2j = 56) instead of block Sturm counts.
+// Read per call (tests flip it inside one process).
+bool pairs_dense_eig() {
+    const char* de = getenv("KT_PAIRS_DENSE_EIG");
+    return de && de[0] == '1';
 }
 
-// Whether k_pair_reg forms the next step's row sums during the eigenvalues
-// (spec: one more n x 2 LDS block); the weights leave the LDS for it (csr 2
-// -> 1: read from global memory, L2-resident) when both do not fit.
-static int reg_spec_fits(int n, int64_t nnz, int it, bool has_long, int& csr, size_t lds_max) {
-    if (!KT_REG_SPEC) return 0;
-    if (reg_lds_layout(n, nnz, it, has_long, csr, true).total <= lds_max) return 1;
-    if (csr == 2 && reg_lds_layout(n, nnz, it, has_long, 1, true).total <= lds_max) {
-        csr = 1;
-        return 1;
+// How k_pair_reg runs on an n x n matrix of nnz nonzeros for up to `it` steps,
+// decided in ONE place: the LDS is sized for exactly the layout the kernel
+// instance then uses.
+//   applies: register-resident runs up to 8 rows per thread, block Sturm
+//     eigenvalues only (KT_PAIRS_REG=0 keeps k_pair_fused), the gather block
+//     and the eigen workspace fit the LDS beside the kernel's static
+//     __shared__;
+//   csr: as much of the CSR as fits too -- 1 = row pointers + u16 columns,
+//     2 = and the weights (never for unit weights: they are not read);
+//   spec: the next step's row sums are formed during the eigenvalues (one more
+//     n x 2 LDS block); the weights leave the LDS for it (csr 2 -> 1: read
+//     from global memory, L2-resident) when both do not fit;
+//   rows per thread: 2, 4, then exact from 6 (one row more costs ~12 VGPRs:
+//     at R = 8 the kernel spills 6-18 VGPRs to scratch at 2 waves per SIMD,
+//     R = 7 and below do not -- India, n = 3,228, takes R = 7).
+struct PairRegPlan {
+    bool applies;
+    int csr, spec, rows;
+    size_t lds_bytes;
+};
+static PairRegPlan pair_reg_plan(int n, int64_t nnz, int it, int n_long, bool unit) {
+    constexpr size_t kLdsMax = 160 * 1024 - 2048;  // less the kernel's static __shared__
+    const bool has_long = std::min(n_long, kRegLongCap) > 0;
+    auto fits = [&](int csr, bool spec) { return reg_lds_layout(n, nnz, it, has_long, csr, spec).total <= kLdsMax; };
+    const char* rg = getenv("KT_PAIRS_REG");
+    PairRegPlan p{false, 0, 0, 0, 0};
+    p.applies = !pairs_dense_eig() && !(rg && rg[0] == '0') && n >= 2 && n <= 8 * kFusedThreads &&
+                nnz < (int64_t)1 << 31 && fits(0, false);
+    if (!p.applies) return p;
+    for (int cand = unit ? 1 : 2; cand >= 1 && p.csr == 0; --cand)
+        if (fits(cand, false)) p.csr = cand;
+    if (KT_REG_SPEC) {
+        if (fits(p.csr, true)) {
+            p.spec = 1;
+        } else if (p.csr == 2 && fits(1, true)) {
+            p.csr = 1;
+            p.spec = 1;
+        }
     }
-    return 0;
+    p.lds_bytes = reg_lds_layout(n, nnz, it, has_long, p.csr, p.spec).total;
+    const int rows = (n + kFusedThreads - 1) / kFusedThreads;
+    p.rows = rows <= 2 ? 2 : rows <= 4 ? 4 : rows <= 6 ? 6 : rows;
+    return p;
 }
 
 bool pair_reg_applies(int n, int64_t nnz, int it, int n_long, bool unit) {
-    const char* de = getenv("KT_PAIRS_DENSE_EIG");
-    const char* rg = getenv("KT_PAIRS_REG");
-    constexpr size_t kLdsMax = 160 * 1024 - 2048;
-    const bool has_long = std::min(n_long, kRegLongCap) > 0;
-    (void)unit;
-    return !(de && de[0] == '1') && !(rg && rg[0] == '0') && n >= 2 && n <= 8 * kFusedThreads &&
-           nnz < (int64_t)1 << 31 && reg_lds_layout(n, nnz, it, has_long, 0).total <= kLdsMax;
+    return pair_reg_plan(n, nnz, it, n_long, unit).applies;
+}
+
+// the k_pair_reg<R, CSR> instance of a plan; dyn: see launch_pair_reg_dyn
+static hipError_t launch_pair_reg(const PairRegPlan& p, int C, int n, int64_t nnz, const FusedCSR& M, const int* ii,
+                                  const int* jj, const double* B, int it, int fun, double tol, double* state,
+                                  const int* dyn, hipStream_t st) {
+    if (!p.applies) return hipErrorInvalidValue;
+#define KT_REG_LAUNCH(RR, CC)                                                                                   \
+    k_pair_reg<RR, CC><<<C, kFusedThreads, p.lds_bytes, st>>>(C, n, (int)nnz, M, ii, jj, B[0], B[1], B[2], B[3], it, \
+                                                              fun, tol, state, dyn, p.spec)
+#define KT_REG_CSR(RR)                         \
+    if (p.csr == 0) KT_REG_LAUNCH(RR, 0);      \
+    else if (p.csr == 1) KT_REG_LAUNCH(RR, 1); \
+    else KT_REG_LAUNCH(RR, 2)
+    if (p.rows == 2) { KT_REG_CSR(2); }
+    else if (p.rows == 4) { KT_REG_CSR(4); }
+    else if (p.rows == 6) { KT_REG_CSR(6); }
+    else if (p.rows == 7) { KT_REG_CSR(7); }
+    else { KT_REG_CSR(8); }
+#undef KT_REG_CSR
+#undef KT_REG_LAUNCH
+    return hipGetLastError();
 }
 
 // k_pair_reg on candidates ii/jj (device) with the CSR's nnz / n_long read
-// from dyn; nnz_max / has_long_max size the LDS (the first step's matrix)
+// from dyn; nnz_max and A.n_long size the LDS (the first step's matrix)
 hipError_t launch_pair_reg_dyn(int C, int n, int64_t nnz_max, const CsrView& A, bool unit, const int* ii,
                                const int* jj, const double* B, int it, int fun, double tol, double* state,
                                const int* dyn, hipStream_t st) {
     if (C <= 0) return hipSuccess;
     const FusedCSR M{A.rp, A.ci, A.va, A.long_rows, A.n_long, A.long_thresh, unit ? 1 : 0};
-    constexpr size_t kLdsMax = 160 * 1024 - 2048;
-    const bool has_long = std::min(A.n_long, kRegLongCap) > 0;
-    int csr = 0;
-    for (int cand = unit ? 1 : 2; cand >= 1; --cand)
-        if (reg_lds_layout(n, nnz_max, it, has_long, cand).total <= kLdsMax) {
-            csr = cand;
-            break;
-        }
-    const int spec = reg_spec_fits(n, nnz_max, it, has_long, csr, kLdsMax);
-    const size_t lds = reg_lds_layout(n, nnz_max, it, has_long, csr, spec).total;
-    const int rr = reg_rows(n);
-#define KT_REG_LAUNCH(RR, CC)                                                                                  \
-    k_pair_reg<RR, CC><<<C, kFusedThreads, lds, st>>>(C, n, (int)nnz_max, M, ii, jj, B[0], B[1], B[2], B[3], it, \
-                                                      fun, tol, state, dyn, spec)
-#define KT_REG_CSR(RR)                       \
-    if (csr == 0) KT_REG_LAUNCH(RR, 0);      \
-    else if (csr == 1) KT_REG_LAUNCH(RR, 1); \
-    else KT_REG_LAUNCH(RR, 2)
-    if (rr == 2) { KT_REG_CSR(2); }
-    else if (rr == 4) { KT_REG_CSR(4); }
-    else if (rr == 6) { KT_REG_CSR(6); }
-    else if (rr == 7) { KT_REG_CSR(7); }
-    else { KT_REG_CSR(8); }
-#undef KT_REG_CSR
-#undef KT_REG_LAUNCH
-    return hipGetLastError();
+    return launch_pair_reg(pair_reg_plan(n, nnz_max, it, A.n_long, unit), C, n, nnz_max, M, ii, jj, B, it, fun, tol,
+                           state, dyn, st);
 }
 
 hipError_t launch_greedy_edit(int C, const double* state, int* Ti, int* Tj, int nT, int n, int long_thresh,
@@ -2568,45 +2410,10 @@ hipError_t launch_pair_fused(int C, int n, int64_t nnz, const CsrView& A, bool u
                              double* big, int64_t big_stride, double* state, hipStream_t st) {
     if (C <= 0) return hipSuccess;
     const FusedCSR M{A.rp, A.ci, A.va, A.long_rows, A.n_long, A.long_thresh, unit ? 1 : 0};
-    // KT_PAIRS_DENSE_EIG=1: the dense tridiagonalisation + multisection in LDS
-    // (and the one-thread solver past 2j = 56) instead of block Sturm counts
-    const char* de = getenv("KT_PAIRS_DENSE_EIG");
-    const int blk_eig = !(de && de[0] == '1');
-    // register-resident runs (k_pair_reg) up to 8 rows per thread; KT_PAIRS_REG=0 keeps k_pair_fused.
-    // LDS: the gather block and the eigen workspace, then as much of the CSR as
-    // fits (row pointers + u16 columns, then the weights).
-    const char* rg = getenv("KT_PAIRS_REG");
-    constexpr size_t kLdsMax = 160 * 1024 - 2048;  // static __shared__ of the kernel
-    const bool has_long = std::min(A.n_long, kRegLongCap) > 0;
-    if (blk_eig && !(rg && rg[0] == '0') && n >= 2 && n <= 8 * kFusedThreads && nnz < (int64_t)1 << 31 &&
-        reg_lds_layout(n, nnz, it, has_long, 0).total <= kLdsMax) {
-        int csr = 0;
-        for (int cand = unit ? 1 : 2; cand >= 1; --cand)
-            if (reg_lds_layout(n, nnz, it, has_long, cand).total <= kLdsMax) {
-                csr = cand;
-                break;
-            }
-        const int spec = reg_spec_fits(n, nnz, it, has_long, csr, kLdsMax);
-        const size_t lds = reg_lds_layout(n, nnz, it, has_long, csr, spec).total;
-        const int rr = reg_rows(n);
-#define KT_REG_LAUNCH(RR, CC)                                                                                  \
-    k_pair_reg<RR, CC><<<C, kFusedThreads, lds, st>>>(C, n, (int)nnz, M, ii, jj, B[0], B[1], B[2], B[3], it, fun, \
-                                                      tol, state, nullptr, spec)
-#define KT_REG_CSR(RR)                       \
-    if (csr == 0) KT_REG_LAUNCH(RR, 0);      \
-    else if (csr == 1) KT_REG_LAUNCH(RR, 1); \
-    else KT_REG_LAUNCH(RR, 2)
-        if (rr == 2) { KT_REG_CSR(2); }
-        else if (rr == 4) { KT_REG_CSR(4); }
-        else if (rr == 6) { KT_REG_CSR(6); }
-        else if (rr == 7) { KT_REG_CSR(7); }
-        else { KT_REG_CSR(8); }
-#undef KT_REG_CSR
-#undef KT_REG_LAUNCH
-        return hipGetLastError();
-    }
+    const PairRegPlan plan = pair_reg_plan(n, nnz, it, A.n_long, unit);
+    if (plan.applies) return launch_pair_reg(plan, C, n, nnz, M, ii, jj, B, it, fun, tol, state, nullptr, st);
     k_pair_fused<<<C, kFusedThreads, pair_fused_lds_bytes(it), st>>>(
-        C, n, M, ii, jj, B[0], B[1], B[2], B[3], it, fun, tol, vec, big, big_stride, state, blk_eig);
+        C, n, M, ii, jj, B[0], B[1], B[2], B[3], it, fun, tol, vec, big, big_stride, state, pairs_dense_eig() ? 0 : 1);
     return hipGetLastError();
 }
 
@@ -2627,8 +2434,7 @@ __global__ void k_pair_active(int C, const double* __restrict__ state, int* __re
 hipError_t launch_pair_eig(int C, int j, int it, int fun, double tol, const double* hist,
                            const double* Cm, double* scratch, int64_t sstride, double* state,
                            int* active, hipStream_t st) {
-    const char* de = getenv("KT_PAIRS_DENSE_EIG");
-    if (!(de && de[0] == '1')) {  // block Sturm counts: no LDS limit, no one-thread fallback
+    if (!pairs_dense_eig()) {  // block Sturm counts: no LDS limit, no one-thread fallback
         const size_t lds = sizeof(double) * (11 * (size_t)j + 14 * (size_t)j + 4 * (size_t)j);
         k_pair_eig_blk<<<C, kFusedThreads, lds, st>>>(C, j, it, fun, tol, hist, Cm, state);
     } else if (2 * j <= 56) {  // 2 nn^2 + 6 nn doubles <= 52 KB of LDS

@@ -730,7 +730,6 @@ static void slq_collect(kt_matrix_s* A, int ticket, double* sum_q, double* sum_q
     double* htrec = w.host_trec[slot].as<double>();
     KT_HIP(hipSetDevice(ctx->device));
     for (int l = 0; l < pd.lanes; ++l) KT_HIP(hipEventSynchronize(pd.done[l]));
-#if !defined(KT_KY_DIAG) || KT_KY_DIAG == 0  // (diagnostic builds time the pass alone: no redo)
     if (ctx->yform) {  // sweeps with a guarded probe are redone by the explicit CGS2 sweep
         const DevCSR& H = hub_csr(A);
         int64_t redone = 0;
@@ -747,7 +746,6 @@ static void slq_collect(kt_matrix_s* A, int ticket, double* sum_q, double* sum_q
         }
         ctx->yform_redone += redone;
     }
-#endif
     // host Gauss quadrature, 16 probes per task on the persistent pool
     // (threads spawned and joined per call cost ~0.1-0.3 ms per call)
     std::vector<double> qv((size_t)nprobes);

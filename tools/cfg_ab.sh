@@ -1,5 +1,6 @@
 #!/bin/bash
-# Same-box A/B of var/kk_nodpp (-DKT_SHFL_DPP=0) and the in-tree library on the
+# Same-box A/B of var/kk_nodpp (a build with the __shfl_xor forms of kt_wave.h,
+# today -DKT_WAVE_DPP=0; it was measured as -DKT_SHFL_DPP=0) and the in-tree library on the
 # config-1 and config-3 drivers (tests/perf/bench_config{1,3}.py), twice each.
 set -o pipefail
 O=$PWD/gpurun_out/${1:-kk2}; mkdir -p $O

@@ -250,11 +250,17 @@ struct kt_context_s {
 };
 
 namespace kt {
-// One device copy of A as CSR (int32 indices), rows in some order.
+// One device copy of A as CSR (int32 indices), rows in some order.  Columns
+// ascend within every row (build_csr sorts a row it relabels, or that the host
+// copy holds unsorted).
 struct DevCSR {
     int* rowptr = nullptr;
     int* col = nullptr;
     double* val = nullptr;
+    // relabelled (hub) copy only: k = index into col of row r's first entry
+    // with column >= r (rowptr[r + 1] if none), stored as ~k where that entry
+    // is the diagonal -- the strictly-lower prefix of the y-form's last pass
+    int* lower = nullptr;
     int* long_rows = nullptr;  // rows with degree > long_thresh, heaviest first
     int n_long = 0;
     int n_heavy = 0;           // the first n_heavy long rows have degree > kExpmvCoopThresh
@@ -289,7 +295,8 @@ struct kt_matrix_s {
     int long_thresh = 64;
     bool unit_values = false;  // every stored value == 1.0 (unweighted adjacency)
     int symmetric = -1;        // -1 unknown, 0 no, 1 yes (checked on the host copy)
-    // hub: rows relabelled by descending degree (hubs first) for the probe
+    // hub: rows relabelled by descending degree class (hubs first) and, inside
+    // a class, clustered by a shared neighbour (kt_order.h) for the probe
     // hot path; probes stay keyed by ORIGINAL index via hub.perm, so results
     // do not depend on the relabelling.
     kt::DevCSR hub;

@@ -2,7 +2,8 @@
 //
 // Data layout in HBM:
 //   A      : CSR, int32 row_ptr[n+1], int32 col[nnz], fp64 val[nnz]; rows
-//            relabelled by descending degree (kt_runtime.cpp), hub rows first.
+//            relabelled by descending degree class (kt_order.h), hub rows
+//            first, columns ascending within a row.
 //   blocks : n x P fp64, ROW-MAJOR ("probe-contiguous"): row i of a probe
 //            block is P consecutive doubles, so every nonzero a_ic gathers
 //            one contiguous 8P-byte row X[c, 0:P] -- a coalesced 16 B/lane
@@ -511,9 +512,8 @@ __device__ __forceinline__ void ycoef_probe(int p, int P, double d0, double d1, 
 // and writes Out[r] = g t_r - a X[r] - b Yold[r] in place over Yold, with
 // per-probe (g, a, b) = (1, alpha_j, beta_j) / beta_{j+1}.  Start mode
 // (has_old = 0): X = the probe block z, (g, a, b) = (1/||z||, 0, 0), Out =
-// y_0 = A v_0.  partial slabs [3][P][grid]: X.t, X.Out, Out.Out.  Out ==
-// nullptr (the last pass of a sweep): only X.t is formed -- Yold is not read
-// and nothing is stored.
+// y_0 = A v_0.  partial slabs [3][P][grid]: X.t, X.Out, Out.Out.  The last
+// pass of a sweep needs only X.t and is k_spmm_quadform (below).
 // KF_VB (round 6): the pass also forms the normalised Lanczos vector
 //   v_{j+1} = g y_j - a v_j - b v_{j-1}
 // with the SAME per-probe (g, a, b): y_i = A v_i for every i (v_0 is the start
@@ -524,19 +524,14 @@ __device__ __forceinline__ void ycoef_probe(int p, int P, double d0, double d1, 
 // pass, which still owes v_{m-1}.  No extra gathers: +24 n bcols bytes per
 // pass where the explicit sweep's K1 + K2 move 32 n P more.
 // ---------------------------------------------------------------------------
-template <int P, int FLAGS, class G = Geo<P>>
-__device__ __forceinline__ void row_epilogue_y(int row, int p0, const double* s, const double* cg,
-                                               const double* ca, const double* cb, bool has_old,
-                                               const double* __restrict__ X,
-                                               const double* __restrict__ Yold,
-                                               double* __restrict__ Out, double* d0, double* d1,
-                                               double* d2, __amdgpu_buffer_rsrc_t orsrc,
-                                               const double* __restrict__ Vc = nullptr,
-                                               const double* __restrict__ Vo = nullptr,
-                                               double* __restrict__ Vn = nullptr, int bcols = 0) {
+// KF_VB: the row's v_{j+1} from its own y_j (xi) and basis slots
+template <int P, int FLAGS, class G>
+__device__ __forceinline__ void row_basis_y(int64_t off, int p0, const typename VecT<G::VEC>::T& xi,
+                                            const double* cg, const double* ca, const double* cb,
+                                            const double* __restrict__ Vc,
+                                            const double* __restrict__ Vo, double* __restrict__ Vn,
+                                            int bcols) {
     using V = VecT<G::VEC>;
-    const int64_t off = (int64_t)row * P + p0;
-    const typename V::T xi = V::load(X + off);
     if constexpr (FLAGS & KF_VB) {
         if (p0 < bcols) {
             const typename V::T vc = V::load(Vc + off);
@@ -550,11 +545,22 @@ __device__ __forceinline__ void row_epilogue_y(int row, int p0, const double* s,
             }
         }
     }
-    if (!Out) {  // last pass: only alpha (X.t) is still needed
-#pragma unroll
-        for (int e = 0; e < G::VEC; ++e) d0[e] = fma(V::get(xi, e), s[e], d0[e]);
-        return;
-    }
+}
+
+template <int P, int FLAGS, class G = Geo<P>>
+__device__ __forceinline__ void row_epilogue_y(int row, int p0, const double* s, const double* cg,
+                                               const double* ca, const double* cb, bool has_old,
+                                               const double* __restrict__ X,
+                                               const double* __restrict__ Yold,
+                                               double* __restrict__ Out, double* d0, double* d1,
+                                               double* d2, __amdgpu_buffer_rsrc_t orsrc,
+                                               const double* __restrict__ Vc = nullptr,
+                                               const double* __restrict__ Vo = nullptr,
+                                               double* __restrict__ Vn = nullptr, int bcols = 0) {
+    using V = VecT<G::VEC>;
+    const int64_t off = (int64_t)row * P + p0;
+    const typename V::T xi = V::load(X + off);
+    row_basis_y<P, FLAGS, G>(off, p0, xi, cg, ca, cb, Vc, Vo, Vn, bcols);
     typename V::T yo;
     if (has_old) yo = V::load_nt(Yold + off);
     typename V::T o;
@@ -798,6 +804,110 @@ __global__ __launch_bounds__(BLOCK) void k_spmm_lanczos(
         double v = 0.0;
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) v += red[w][q][p];
+        partial[(int64_t)t * gridDim.x + blockIdx.x] = v;
+    }
+}
+
+// The last pass of a y-form sweep: y_m is never used, and alpha_{m-1} needs
+// only the quadratic form d0 = X'A X per probe.  A is symmetric (the y-form
+// relies on it), so
+//   X'A X = sum_r X[r] (2 sum_{c < r} a_rc X[c] + a_rr X[r]):
+// the pass gathers each row's strictly-lower prefix alone, half the nonzeros
+// -- and in the hubs-first labelling c < r is the popular endpoint of every
+// edge, the half that hits in L2.  lower[r] (DevCSR::lower) is the index of
+// the row's first entry with column >= r, complemented where that entry is
+// the diagonal.  Same row groups, long-row waves and fixed-order reduction as
+// k_spmm_lanczos; slabs 1 and 2 of partial are written as zeros (k_ycoef
+// reads all three).  KF_VB: the row's v_{m-1} as in k_spmm_lanczos.
+template <int P, int BLOCK, int FLAGS>
+__global__ __launch_bounds__(BLOCK) void k_spmm_quadform(
+    const int* __restrict__ row_ptr, const int* __restrict__ col, const double* __restrict__ val,
+    const int* __restrict__ lower, int n, const double* __restrict__ X,
+    const double* __restrict__ coef, double* __restrict__ partial,
+    const int* __restrict__ long_rows, int n_long, int long_thresh, int long_blocks,
+    const double* __restrict__ Vc, const double* __restrict__ Vo, double* __restrict__ Vn, int bcols) {
+    using G = GeoKY<P>;
+    using V = VecT<G::VEC>;
+    constexpr int WAVES = BLOCK / 64;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int sub = lane % G::LPR;
+    const int grp = lane / G::LPR;
+    const int p0 = sub * G::VEC;
+
+    double d0[G::VEC];
+#pragma unroll
+    for (int e = 0; e < G::VEC; ++e) d0[e] = 0.0;
+    double cg[G::VEC], ca[G::VEC], cb[G::VEC];
+    if constexpr (FLAGS & KF_VB) {
+#pragma unroll
+        for (int e = 0; e < G::VEC; ++e) {
+            cg[e] = coef[p0 + e];
+            ca[e] = coef[P + p0 + e];
+            cb[e] = coef[2 * P + p0 + e];
+        }
+    }
+    // s = the row's strictly-lower sum; lw = lower[row]
+    auto epilogue = [&](int row, int lw, const double* s) {
+        const int64_t off = (int64_t)row * P + p0;
+        const typename V::T xi = V::load(X + off);
+        row_basis_y<P, FLAGS, G>(off, p0, xi, cg, ca, cb, Vc, Vo, Vn, bcols);
+        double arr = 0.0;  // a_rr
+        if (lw < 0) arr = (FLAGS & KF_UNIT) ? 1.0 : val[~lw];
+#pragma unroll
+        for (int e = 0; e < G::VEC; ++e) {
+            const double x = V::get(xi, e);
+            d0[e] = fma(x, fma(2.0, s[e], arr * x), d0[e]);
+        }
+    };
+
+    if ((int)blockIdx.x < long_blocks) {
+        for (int li = blockIdx.x * WAVES + wave; li < n_long; li += long_blocks * WAVES) {
+            const int row = long_rows[li];
+            const int beg = row_ptr[row];
+            const int lw = lower[row];
+            double s[G::VEC];
+#pragma unroll
+            for (int e = 0; e < G::VEC; ++e) s[e] = 0.0;
+            gather_row<P, FLAGS, G>(beg + grp, lw < 0 ? ~lw : lw, G::GPW, p0, col, val, X, s);
+#pragma unroll
+            for (int o = G::LPR; o < 64; o <<= 1)
+#pragma unroll
+                for (int e = 0; e < G::VEC; ++e) s[e] += kt::shfl_xor(s[e], o);
+            if (grp == 0) epilogue(row, lw, s);
+        }
+    } else {
+        const int sb = blockIdx.x - long_blocks;
+        const int groups_total = (gridDim.x - long_blocks) * WAVES * G::GPW;
+        for (int row = (sb * WAVES + wave) * G::GPW + grp; row < n; row += groups_total) {
+            const int beg = row_ptr[row];
+            const int end = row_ptr[row + 1];
+            if (end - beg > long_thresh) continue;  // owned by a long-row wave
+            const int lw = lower[row];
+            double s[G::VEC];
+#pragma unroll
+            for (int e = 0; e < G::VEC; ++e) s[e] = 0.0;
+            gather_row<P, FLAGS, G>(beg, lw < 0 ? ~lw : lw, 1, p0, col, val, X, s);
+            epilogue(row, lw, s);
+        }
+    }
+
+#pragma unroll
+    for (int o = G::LPR; o < 64; o <<= 1)
+#pragma unroll
+        for (int e = 0; e < G::VEC; ++e) d0[e] += kt::shfl_xor(d0[e], o);
+    __shared__ double red[WAVES][P];
+    if (grp == 0) {
+#pragma unroll
+        for (int e = 0; e < G::VEC; ++e) red[wave][p0 + e] = d0[e];
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < 3 * P; t += BLOCK) {  // slot t = q * P + p
+        double v = 0.0;
+        if (t < P) {
+#pragma unroll
+            for (int w = 0; w < WAVES; ++w) v += red[w][t];
+        }
         partial[(int64_t)t * gridDim.x + blockIdx.x] = v;
     }
 }
@@ -2284,6 +2394,28 @@ hipError_t launch_spmm_lanczos(int P, int flags, int grid, const int* rp, const 
         default: KT_KY(KF_UNIT | KF_SC1); break;
         }
 #undef KT_KY
+    });
+}
+
+hipError_t launch_spmm_quadform(int P, int flags, int grid, const int* rp, const int* ci,
+                                const double* va, const int* lower, int n, const double* X,
+                                const double* coef, double* partial, const int* long_rows, int n_long,
+                                int long_thresh, int long_blocks, hipStream_t st, const double* Vc,
+                                const double* Vo, double* Vn, int bcols) {
+    return dispatch_p(P, [&](auto c) {
+        constexpr int PP = decltype(c)::value;
+#define KT_KQ(F)                                                                                    \
+    k_spmm_quadform<PP, kBlock, F><<<grid, kBlock, 0, st>>>(rp, ci, va, lower, n, X, coef, partial, \
+                                                            long_rows, n_long, long_thresh,         \
+                                                            long_blocks, Vc, Vo, Vn, bcols)
+        if (Vn) {
+            if (flags & KF_UNIT) KT_KQ(KF_UNIT | KF_VB);
+            else KT_KQ(KF_VB);
+        } else {
+            if (flags & KF_UNIT) KT_KQ(KF_UNIT);
+            else KT_KQ(0);
+        }
+#undef KT_KQ
     });
 }
 

@@ -95,6 +95,15 @@ hipError_t launch_spmm_lanczos(int P, int flags, int grid, const int* rp, const 
                                const int* long_rows, int n_long, int long_thresh, int long_blocks,
                                hipStream_t st, const double* Vc = nullptr, const double* Vo = nullptr,
                                double* Vn = nullptr, int bcols = 0);
+// The last pass of a y-form sweep: only slab 0, X'A X per probe, from each
+// row's strictly-lower prefix and diagonal (lower = DevCSR::lower; slabs 1, 2
+// are written as zeros).  Vn as above.
+hipError_t launch_spmm_quadform(int P, int flags, int grid, const int* rp, const int* ci,
+                                const double* va, const int* lower, int n, const double* X,
+                                const double* coef, double* partial, const int* long_rows, int n_long,
+                                int long_thresh, int long_blocks, hipStream_t st,
+                                const double* Vc = nullptr, const double* Vo = nullptr,
+                                double* Vn = nullptr, int bcols = 0);
 hipError_t launch_rademacher_signs(int P, int n, uint64_t seed, int64_t probe_base,
                                   const int* perm, uint32_t* S, hipStream_t st);
 hipError_t launch_spmm_lanczos_start(int P, int flags, int grid, const int* rp, const int* ci,

@@ -11,6 +11,7 @@
 
 #include "kt_internal.h"
 #include "kt_launch.h"
+#include "kt_order.h"
 #include "kt_pool.h"
 
 namespace kt {
@@ -128,7 +129,7 @@ void DevCSR::release() {
     if (blob) (void)hipFree(blob);
     blob = nullptr;
     blob_bytes = 0;
-    rowptr = col = long_rows = perm = med_rows = short_tasks = med_tasks = nullptr;
+    rowptr = col = lower = long_rows = perm = med_rows = short_tasks = med_tasks = nullptr;
     ck_beg = ck_end = sp_rows = sp_first = nullptr;
     val = nullptr;
     n_long = n_heavy = n_med = n_short = n_chunks = n_split = 0;
@@ -168,6 +169,19 @@ void build_csr(kt_matrix_s* A, const std::vector<int32_t>& new2old, DevCSR& out,
         for (size_t t = 0; t < tmp.size(); ++t) {
             c32[rp32[r] + t] = tmp[t].first;
             v64[rp32[r] + t] = tmp[t].second;
+        }
+    }
+    // columns ascend within a row from here on; the relabelled copy's
+    // strictly-lower prefix per row (DevCSR::lower)
+    std::vector<int32_t> low;
+    if (!ident) {
+        low.resize(n);
+        for (int64_t r = 0; r < n; ++r) {
+            const int32_t* cb = c32.data() + rp32[r];
+            const int32_t* ce = c32.data() + rp32[r + 1];
+            const int32_t* it = std::lower_bound(cb, ce, (int32_t)r);
+            const int32_t k = (int32_t)(it - c32.data());
+            low[r] = (it != ce && *it == (int32_t)r) ? ~k : k;
         }
     }
     std::vector<int32_t> lr;
@@ -270,6 +284,7 @@ void build_csr(kt_matrix_s* A, const std::vector<int32_t>& new2old, DevCSR& out,
         add(out.sp_first, spf.data(), sizeof(int) * spf.size());
     }
     if (!ident) add(out.perm, new2old.data(), sizeof(int) * n);
+    if (!ident) add(out.lower, low.data(), sizeof(int) * n);
     auto slice = [](size_t b) { return (std::max<size_t>(b, 16) + 255) & ~(size_t)255; };
     size_t total = 0;
     for (const Seg& g : segs) total += slice(g.bytes);
@@ -290,7 +305,7 @@ void build_csr(kt_matrix_s* A, const std::vector<int32_t>& new2old, DevCSR& out,
         char* h = out.stage.as<char>();
         size_t off = 0;
         out.ck_beg = out.ck_end = out.sp_rows = out.sp_first = nullptr;
-        out.perm = nullptr;
+        out.perm = out.lower = nullptr;
         out.short_tasks = out.med_tasks = nullptr;
         for (const Seg& g : segs) {
             if (g.bytes) std::memcpy(h + off, g.src, g.bytes);
@@ -331,13 +346,9 @@ void refresh_device(kt_matrix_s* A) {
 const DevCSR& hub_csr(kt_matrix_s* A) {
     if (A->hub.built) return A->hub;
     const int64_t n = A->n;
-    // degree-descending relabelling (stable, so ties keep original order)
-    A->new2old.resize(n);
+    // hubs first, neighbour-clustered inside a degree class (kt_order.h)
+    hub_order(n, A->h_rowptr.data(), A->h_col.data(), A->long_thresh, A->new2old);
     A->old2new.resize(n);
-    for (int64_t i = 0; i < n; ++i) A->new2old[i] = (int32_t)i;
-    std::stable_sort(A->new2old.begin(), A->new2old.end(), [&](int32_t a, int32_t b) {
-            return A->h_rowptr[a + 1] - A->h_rowptr[a] > A->h_rowptr[b + 1] - A->h_rowptr[b];
-        });
     for (int64_t r = 0; r < n; ++r) A->old2new[A->new2old[r]] = (int32_t)r;
     build_csr(A, A->new2old, A->hub);
     return A->hub;

@@ -163,6 +163,7 @@ YSweep::YSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, uint64_t seed_
     kt_context_s* ctx = A->ctx;
     n = (int)A->n;
     if (lane < 0 || lane > 3) fail(KT_ERR_ARG, "sweep lane out of range");
+    if (!M.lower) fail(KT_ERR_ARG, "y-form sweep: the CSR copy has no lower-prefix array");
     if (lane && !ctx->aux_stream[lane - 1])
         KT_HIP(hipStreamCreateWithFlags(&ctx->aux_stream[lane - 1], hipStreamNonBlocking));
     st = lane ? ctx->aux_stream[lane - 1] : ctx->stream;
@@ -205,10 +206,13 @@ void YSweep::start() {
 void YSweep::step(int j) {
     kt_context_s* ctx = A->ctx;
     prof_begin(ctx, PROF_SPMM, st, P);
-    const bool last = j + 2 == m;  // y_{m} is never used: alpha_{m-1} needs only X.t
-    KT_HIP(launch_spmm_lanczos(P, flags, grid1, M.rowptr, M.col, M.val, n, Xc, last ? nullptr : Yo,
-                               last ? nullptr : Ot, ys + 6 * P, part, M.long_rows, M.n_long, A->long_thresh,
-                               lblocks, st));
+    const bool last = j + 2 == m;  // y_{m} is never used: alpha_{m-1} needs only X'A X
+    if (last)
+        KT_HIP(launch_spmm_quadform(P, flags, grid1, M.rowptr, M.col, M.val, M.lower, n, Xc, ys + 6 * P, part,
+                                    M.long_rows, M.n_long, A->long_thresh, lblocks, st));
+    else
+        KT_HIP(launch_spmm_lanczos(P, flags, grid1, M.rowptr, M.col, M.val, n, Xc, Yo, Ot, ys + 6 * P, part,
+                                   M.long_rows, M.n_long, A->long_thresh, lblocks, st));
     prof_end(ctx, PROF_SPMM, st);
     KT_HIP(launch_ycoef(P, part, grid1, 0, last, 0.0, ys, rec_at(0, j + 1), rec_at(1, j + 1), rec_at(2, j + 1),
                         guard, st));
@@ -236,6 +240,7 @@ YBlockSweep::YBlockSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, cons
     kt_context_s* ctx = A->ctx;
     n = (int)A->n;
     if (lane < 0 || lane > 3) fail(KT_ERR_ARG, "sweep lane out of range");
+    if (!M.lower) fail(KT_ERR_ARG, "y-form sweep: the CSR copy has no lower-prefix array");
     if (ncols < 1 || ncols > P) fail(KT_ERR_ARG, "y-form block sweep: 1 <= ncols <= P");
     if (lane && !ctx->aux_stream[lane - 1])
         KT_HIP(hipStreamCreateWithFlags(&ctx->aux_stream[lane - 1], hipStreamNonBlocking));
@@ -280,10 +285,15 @@ void YBlockSweep::start() {
 void YBlockSweep::step(int j) {
     const bool last = j + 2 == m;
     prof_begin(A->ctx, PROF_YBLOCK, st, P);
-    KT_HIP(launch_spmm_lanczos(P, flags, grid1, M.rowptr, M.col, M.val, n, Xc, last ? nullptr : Yo,
-                               last ? nullptr : Ot, ys + 6 * P, part, M.long_rows, M.n_long, A->long_thresh, lblocks,
-                               st, basis ? slot(j) : nullptr, (basis && j > 0) ? slot(j - 1) : nullptr,
-                               basis ? slot(j + 1) : nullptr, bcols));
+    const double* vc = basis ? slot(j) : nullptr;
+    const double* vo = (basis && j > 0) ? slot(j - 1) : nullptr;
+    double* vn = basis ? slot(j + 1) : nullptr;
+    if (last)
+        KT_HIP(launch_spmm_quadform(P, flags, grid1, M.rowptr, M.col, M.val, M.lower, n, Xc, ys + 6 * P, part,
+                                    M.long_rows, M.n_long, A->long_thresh, lblocks, st, vc, vo, vn, bcols));
+    else
+        KT_HIP(launch_spmm_lanczos(P, flags, grid1, M.rowptr, M.col, M.val, n, Xc, Yo, Ot, ys + 6 * P, part,
+                                   M.long_rows, M.n_long, A->long_thresh, lblocks, st, vc, vo, vn, bcols));
     prof_end(A->ctx, PROF_YBLOCK, st);
     KT_HIP(launch_ycoef(P, part, grid1, 0, last, 0.0, ys, rec_at(0, j + 1), rec_at(1, j + 1), rec_at(2, j + 1), guard,
                         st));

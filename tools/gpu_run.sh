@@ -85,7 +85,7 @@ rehearse)
 pmc)
     SEC=${SECTION:-sf1m}
     B="$REPO/bench.py --full --steps 1 --warmup 1 --cpu-seconds 0 --lanes 1 --mc-steps 1 --no-profile $*"
-    R="spmm_dot|spmm_lanczos|k_update"
+    R="spmm_dot|spmm_lanczos|spmm_quadform|k_update"
     ( cd /tmp && timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$R" -d $O/pmc_fetch -o f --output-format csv -- python3 $B > $O/pmc_fetch.log 2>&1 ) || { tail -20 $O/pmc_fetch.log; exit 1; }
     ( cd /tmp && timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$R" -d $O/pmc_write -o w --output-format csv -- python3 $B > $O/pmc_write.log 2>&1 ) || { tail -20 $O/pmc_write.log; exit 1; }
     ( cd /tmp && timeout -s KILL 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --kernel-include-regex "$R" -d $O/pmc_hit -o h --output-format csv -- python3 $B > $O/pmc_hit.log 2>&1 ) || { tail -20 $O/pmc_hit.log; exit 1; }

@@ -27,7 +27,7 @@ def hub_relabel(A):
     old2new[new2old] = np.arange(A.shape[0])
     B = A[new2old][:, new2old].tocsr()
     B.sort_indices()
-    return B
+    return B, new2old
 
 
 def run(lib, A, order, xoff, P=16, inflight=2048, l2=4 << 20, bypass=0):
@@ -80,19 +80,26 @@ def main():
     ap.add_argument("--inflight", type=int, default=2048)
     ap.add_argument("--schedules", default="baseline")
     ap.add_argument("--bypass", type=int, default=0, help="1: row streams skip L2, 2: CSR skips L2, 3: both")
+    ap.add_argument("--relabel", default="", help="a relabel_* function of schedules.py applied on top of hubs-first")
+    ap.add_argument("--l2-mib", type=float, default=4.0, help="L2 per XCD (2: two sweep lanes share each L2)")
     args = ap.parse_args()
     from krylov_robustness_amd import graphs
     t0 = time.time()
     A = graphs.chung_lu(args.n, args.nnz, gamma=2.5, seed=0)
-    A = hub_relabel(A)
-    print(f"graph n={A.shape[0]} nnz={A.nnz} ({time.time() - t0:.1f} s)", flush=True)
-    lib = load()
+    A, orig = hub_relabel(A)
     import schedules
+    if args.relabel:
+        p = getattr(schedules, args.relabel)(A, orig)
+        A = A[p][:, p].tocsr()
+        A.sort_indices()
+    print(f"graph n={A.shape[0]} nnz={A.nnz} relabel={args.relabel or 'hubs-first'} "
+          f"L2 {args.l2_mib:g} MiB ({time.time() - t0:.1f} s)", flush=True)
+    lib = load()
     for name in args.schedules.split(","):
         t0 = time.time()
         order, xoff = baseline_schedule(A) if name == "baseline" else getattr(schedules, name)(A)
         assert np.array_equal(np.sort(order), np.arange(A.shape[0]))
-        r = run(lib, A, order, xoff, inflight=args.inflight, bypass=args.bypass)
+        r = run(lib, A, order, xoff, inflight=args.inflight, l2=int(args.l2_mib * (1 << 20)), bypass=args.bypass)
         loads = [int(A.indptr[order[xoff[k]:xoff[k + 1]] + 1].sum() - A.indptr[order[xoff[k]:xoff[k + 1]]].sum())
                  for k in range(8)]
         print(f"{name:24s} gather hit {r['gather_hit']:.3f}  stream hit {r['stream_hit']:.3f}  "

@@ -1,4 +1,5 @@
-"""Row -> XCD schedules for run.py (each returns order, xoff)."""
+"""Row -> XCD schedules for run.py (each returns order, xoff), and physical
+relabellings (relabel_*: each returns new2old over the hubs-first labels)."""
 import numpy as np
 
 
@@ -105,3 +106,23 @@ def hgroup_0_64k(A):
 
 def hgroup_4k_16k_prim(A):
     return _hgroup(A, 4096, 16384, _primary(A, 4096))
+
+
+def _relabel_primary(A, orig, exact, t0=4096, long_thresh=64):
+    """The library's row order (csrc/kt_order.h hub_order) as a PHYSICAL
+    relabelling of the hubs-first graph A -- rows and columns both move, where
+    the schedules above only reorder processing: degree class descending
+    (ceil(deg / 4) up to long_thresh and the exact degree above it, or the
+    exact degree throughout), then the highest-degree neighbour of degree rank
+    >= t0, then the original index orig[r] of hubs-first row r."""
+    deg = np.diff(A.indptr)
+    cls = deg if exact else np.where(deg > long_thresh, deg, (deg + 3) // 4)
+    return np.lexsort((orig, _primary(A, t0), -cls))
+
+
+def relabel_primary_quad(A, orig):
+    return _relabel_primary(A, orig, exact=False)
+
+
+def relabel_primary_exact(A, orig):
+    return _relabel_primary(A, orig, exact=True)

@@ -167,7 +167,13 @@ int kt_fun_and_grad_krylov_fun(kt_matrix_t A, int64_t nomega, const double* X, c
 enum kt_afun { /* the Afun argument of mc_trace.m:1 */
     KT_AFUN_MATRIX = 0,  /* Afun is the matrix itself (mc_trace.m:32-34)              */
     KT_AFUN_LANCZOS = 1, /* f(A) x by m-step Lanczos (north star)   */
-    KT_AFUN_EXPMV = 2    /* @(x) expmv(1, A, x, [], 'double') (trace_exp.m:5)          */
+    KT_AFUN_EXPMV = 2,   /* @(x) expmv(1, A, x, [], 'double') (trace_exp.m:5)          */
+    /* KT_AFUN_LANCZOS with the depth chosen per column by a stopping test
+     * (kt_lanczos_fmv_auto below).  The `m` argument of kt_mc_trace,
+     * kt_mc_trace_sharded and kt_trace_exp is then the depth cap m_max: m <= 0
+     * means 128, at most 256.  A column that reaches the cap unconverged is
+     * not an error: the call returns KT_OK and kt_context_stat 6 counts it. */
+    KT_AFUN_LANCZOS_AUTO = 3
 };
 
 /* [tr, res, it] = mc_trace(Afun, n, tol, maxit, isAreal, debug) (mc_trace.m:1):
@@ -208,6 +214,22 @@ int kt_expmv(kt_matrix_t A, double t, int64_t ncols, const double* B, double* F,
  * Afun handle).  X, Y: n x ncols column-major, ncols <= 128. */
 int kt_lanczos_fmv(kt_matrix_t A, int fun, int m, int64_t ncols, const double* X, double* Y);
 
+/* kt_lanczos_fmv with an error-controlled depth: column c runs Lanczos steps
+ * until its own stopping test holds, at most m_max (m_max <= 0: 128; at most
+ * 256), and its result is formed from its record truncated at depth[c], so
+ * it does not depend on the columns it shares a call with.  The test, at
+ * depth j >= 8 on T_j (theta_i, first / last eigenvector rows s_1i, s_ji):
+ *   q_j = sum_i s_1i^2 f(theta_i):  |q_j - q_{j-1}| <= rtol |q_j|  and
+ *                                   |q_{j-1} - q_{j-2}| <= rtol |q_{j-1}|,
+ *   and, when Y is asked for,  beta_j |sum_i s_ji s_1i f(theta_i)|
+ *                                   <= rtol (sum_i s_1i^2 f(theta_i)^2)^(1/2);
+ * a lucky breakdown (beta < 1e-8) or a zero column stops at once.
+ * rtol <= 0: the default, 1e-12.  Y (n x ncols) and quad[c] = x_c' f(A) x_c:
+ * each optional, at least one required; depth (ncols) and capped (the number
+ * of columns that reached m_max unconverged) optional.  ncols <= 128. */
+int kt_lanczos_fmv_auto(kt_matrix_t A, int fun, int m_max, double rtol, int64_t ncols, const double* X,
+                        double* Y, double* quad, int* depth, int* capped);
+
 /* [Q, R] = qr(W, 0) on the device (MATLAB's economy Householder QR: LAPACK
  * reflector signs, tau = 0 completions of exactly dependent columns), the
  * factorisation lanczos_krylov.m:90, arnoldi_krylov.m:99 and mc_trace.m use.
@@ -231,6 +253,16 @@ int kt_host_sym_eig(int n, const double* A, double* w, double* V);
  * weights of the Lanczos-f Afun, f(A) x = ||x|| V f(T) e1).  fun: KT_FUN_*.
  * Pure host code (no device needed). */
 int kt_host_tridiag_quad(int m, const double* alpha, const double* off, int fun, double* q, double* fe1);
+
+/* The stopping test of the adaptive Lanczos depth (kt_lanczos_fmv_auto) at
+ * depth j, 1 <= j <= 256, on one column's tridiagonal: alpha (j), off (j - 1
+ * averaged off-diagonals; with want_fe1 != 0 one more, off[j-1] = beta_j, the
+ * next one).  An off-diagonal below 1e-8 cuts T there (the lucky breakdown)
+ * and sets *converged; below depth 8 nothing else does.  *q = e1' f(T) e1 on
+ * the rows used (fun = KT_FUN_EXP: scaled by exp(-theta_max), so it stays
+ * finite).  rtol <= 0: the default.  Pure host code (no device needed). */
+int kt_host_quad_converged(int j, const double* alpha, const double* off, int fun, int want_fe1,
+                           double rtol, int* converged, double* q);
 
 /* ---- greedy edge selection (krylov_miobi.m / greedy_krylov.m) ---------- */
 
@@ -350,6 +382,9 @@ int kt_debug_delay(kt_context_t ctx, int lane, double microseconds);
  * last fun_update run on this context (n when it went dense).  stat 3: expmv
  * calls (kt_expmv and mc_trace's expmv Afun), stat 4: the Taylor terms they
  * executed (one A b product on the block each, expmv.m:75), since context
+ * creation.  stat 5: the largest Lanczos depth the adaptive Afun
+ * (KT_AFUN_LANCZOS_AUTO, kt_lanczos_fmv_auto) used for a column, stat 6: its
+ * columns that reached the depth cap unconverged, both since context
  * creation. */
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value);
 

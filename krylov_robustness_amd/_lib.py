@@ -34,7 +34,7 @@ class KrylovError(RuntimeError):
 (KT_OK, KT_ERR_ARG, KT_ERR_HIP, KT_ERR_NOT_HERMITIAN, KT_ERR_NOT_SQUARE, KT_ERR_ALLOC, KT_ERR_UNSUPPORTED,
  KT_ERR_CALLBACK) = range(8)
 # kt_afun (mc_trace.m's Afun kinds)
-AFUN_CODES = {"matrix": 0, "lanczos": 1, "expmv": 2}
+AFUN_CODES = {"matrix": 0, "lanczos": 1, "expmv": 2, "lanczos-auto": 3}
 # kt_fun (fun_update.m:43-59)
 FUN_CODES = {"exp": 0, "sinh": 1, "cosh": 2, "sin": 3, "cos": 4, "log": 5, "sqrt": 6}
 
@@ -85,6 +85,8 @@ SIGNATURES = [
     ("kt_trace_exp", C.c_int, [_mat_p, C.c_int, C.c_int, C.c_uint64, _dp]),
     ("kt_expmv", C.c_int, [_mat_p, C.c_double, C.c_int64, _dp, _dp, _ip, _ip, _ip]),
     ("kt_lanczos_fmv", C.c_int, [_mat_p, C.c_int, C.c_int, C.c_int64, _dp, _dp]),
+    ("kt_lanczos_fmv_auto", C.c_int, [_mat_p, C.c_int, C.c_int, C.c_double, C.c_int64, _dp, _dp, _dp, _ip, _ip]),
+    ("kt_host_quad_converged", C.c_int, [C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_double, _ip, _dp]),
     ("kt_trace_fun_update_pairs", C.c_int, [_mat_p, C.c_int64, _i64p, _i64p, _dp, C.c_double,
                                             C.c_double, C.c_int, C.c_int, _dp, _ip, _ip]),
     ("kt_krylov_miobi", C.c_int, [_mat_p, C.c_int, C.c_int64, _i64p, _i64p, C.c_double, C.c_int,

@@ -83,7 +83,8 @@ class Context:
     def stat(self, which: int) -> int:
         """kt_context_stat: 0 y-form sweeps redone, 1 fun_update dense
         fallbacks, 2 basis columns of the last fun_update, 3 expmv calls,
-        4 Taylor terms those calls executed."""
+        4 Taylor terms those calls executed, 5 the largest depth the adaptive
+        Lanczos Afun used, 6 its columns that reached the depth cap."""
         v = C.c_int64()
         _lib.check(_lib.load().kt_context_stat(self._h, int(which), C.byref(v)))
         return int(v.value)
@@ -419,16 +420,29 @@ def fun_and_grad_krylov_fun(X, A, Omega, fun, dfun, dfA, tol, it, debug=False, f
 # ---------------------------------------------------------------------------
 # mc_trace / trace_exp / expmv
 # ---------------------------------------------------------------------------
-def mc_trace(Afun, n=None, tol=1e-3, maxit=10, isAreal=0, debug=0, seed=0, fun="exp", m=30,
+def _afun_depth(kind_name, m) -> int:
+    """The m argument of the Lanczos Afun kinds: the depth (default 30), or
+    for "lanczos-auto" the depth cap (default 0: the library's, 128)."""
+    if m is None:
+        return 0 if kind_name == "lanczos-auto" else 30
+    return int(m)
+
+
+def mc_trace(Afun, n=None, tol=1e-3, maxit=10, isAreal=0, debug=0, seed=0, fun="exp", m=None,
              A=None, ctx: Optional[Context] = None):
     """[tr, res, it] = mc_trace(Afun, n, tol, maxit, isAreal, debug) (mc_trace.m:1).
     Afun: a matrix / DeviceMatrix (mc_trace.m:32-34), or one of the strings
-    "lanczos" (f(A) by m-step Lanczos) / "expmv" (expmv(1, A, .)) with A given."""
+    "lanczos" (f(A) by m-step Lanczos; m defaults to 30) / "lanczos-auto" (the
+    depth chosen per column by a stopping test, m the cap: default 128, at
+    most 256; capped columns are counted by ctx.stat(6)) / "expmv"
+    (expmv(1, A, .)) with A given."""
     if isinstance(Afun, str):
         kind = _lib.AFUN_CODES[Afun]
+        m = _afun_depth(Afun, m)
         D = _dev(A, ctx)
     else:
         kind = _lib.AFUN_CODES["matrix"]
+        m = _afun_depth("matrix", m)
         D = _dev(Afun, ctx)
     if n is not None and int(n) != D.n:
         raise _lib.KrylovError(_lib.KT_ERR_ARG, "n does not match the matrix")
@@ -441,13 +455,14 @@ def mc_trace(Afun, n=None, tol=1e-3, maxit=10, isAreal=0, debug=0, seed=0, fun="
     return float(tr.value), float(res.value), int(it.value)
 
 
-def trace_exp(A, method="lanczos", m=30, seed=0, ctx: Optional[Context] = None) -> float:
+def trace_exp(A, method="lanczos", m=None, seed=0, ctx: Optional[Context] = None) -> float:
     """tr = trace_exp(A) (trace_exp.m:1-7): mc_trace(Afun, n, 1e-4, 1000, 1),
-    Afun = Lanczos-exp (default, the north-star evaluator) or expmv (the
-    reference's own composition)."""
+    Afun = Lanczos-exp at depth m = 30 (default, the north-star evaluator),
+    "lanczos-auto" (error-controlled depth, m the cap: default 128) or expmv
+    (the reference's own composition)."""
     D = _dev(A, ctx)
     tr = C.c_double()
-    _lib.check(_lib.load().kt_trace_exp(D.handle, _lib.AFUN_CODES[method], int(m),
+    _lib.check(_lib.load().kt_trace_exp(D.handle, _lib.AFUN_CODES[method], _afun_depth(method, m),
                                         int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(tr)))
     return float(tr.value)
 
@@ -473,6 +488,30 @@ def lanczos_fmv(A, X, m=30, fun="exp", ctx: Optional[Context] = None):
     _lib.check(_lib.load().kt_lanczos_fmv(D.handle, _fun_code(fun), int(m), X.shape[1], _dptr(X),
                                           _dptr(Y)))
     return Y
+
+
+def lanczos_fmv_auto(A, X, fun="exp", m_max=128, rtol=None, return_info=False, want_y=True,
+                     ctx: Optional[Context] = None):
+    """f(A) X by per-column Lanczos with an error-controlled depth
+    (kt_lanczos_fmv_auto): each column stops by its own test (two consecutive
+    quadrature agreements and the f(T) e1 residual, both at rtol; None: the
+    library's default), at most m_max steps.  Returns Y, or with return_info
+    (Y, info), info = {"quad": x_c' f(A) x_c, "depth": steps per column,
+    "capped": columns that reached m_max unconverged}.  want_y=False skips Y
+    (quadratic forms only: the test drops the residual condition)."""
+    D = _dev(A, ctx)
+    X = _colmajor(X)
+    nc = X.shape[1]
+    Y = np.zeros_like(X, order="F") if want_y else None
+    quad = np.zeros(nc)
+    depth = np.zeros(nc, dtype=np.int32)
+    capped = C.c_int()
+    _lib.check(_lib.load().kt_lanczos_fmv_auto(
+        D.handle, _fun_code(fun), int(m_max), float(rtol) if rtol else 0.0, nc, _dptr(X),
+        _dptr(Y) if want_y else None, _dptr(quad), depth.ctypes.data_as(C.POINTER(C.c_int)), C.byref(capped)))
+    if not return_info:
+        return Y
+    return Y, {"quad": quad, "depth": depth, "capped": int(capped.value)}
 
 
 def function_multiple_entries(A, omega, f="exp", tol=1e-12, it=None, poles=np.inf, debug=0,

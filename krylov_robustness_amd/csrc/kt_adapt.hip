@@ -1,0 +1,244 @@
+// kt_adapt.hip -- device side of the adaptive Lanczos depth (kt_slq.cpp
+// lanczos_columns_adaptive): the per-column stopping test on a sweep's device
+// record, and the back-projection over a basis kept in growth chunks.
+//
+// k_quad_check decides depths only; the values a call returns are formed on
+// the host from the record truncated at the depth chosen here.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "kt_internal.h"
+#include "kt_launch.h"
+
+namespace kt {
+
+namespace {
+
+__device__ __forceinline__ double dev_fscalar(int fun, double x) {
+    switch (fun) {
+    case KT_FUN_EXP: return exp(x);
+    case KT_FUN_SINH: return sinh(x);
+    case KT_FUN_COSH: return cosh(x);
+    case KT_FUN_SIN: return sin(x);
+    case KT_FUN_COS: return cos(x);
+    case KT_FUN_LOG: return log(x);
+    case KT_FUN_SQRT: return sqrt(x);
+    default: return NAN;
+    }
+}
+
+__device__ __forceinline__ double dev_rot_radius(double f, double g) {
+    const double af = fabs(f), ag = fabs(g);
+    const double mx = af > ag ? af : ag;
+    if (mx > 1e150 || (mx < 1e-150 && mx > 0.0)) return hypot(f, g);
+    return sqrt(f * f + g * g);
+}
+
+// The host's implicit-shift QL (kt_dense.cpp ql_rows; EISPACK IMTQL2) on one
+// lane's m x m tridiagonal, arrays strided by G in LDS ([k][lane]); z carries
+// the first row of the eigenvector matrix, zl (LAST) the last row.
+template <bool LAST>
+__device__ void dev_ql_rows(int m, int G, double* d, double* e, double* z, double* zl) {
+    e[(m - 1) * G] = 0.0;
+    for (int i = 0; i < m; ++i) {
+        z[i * G] = (i == 0) ? 1.0 : 0.0;
+        if (LAST) zl[i * G] = (i == m - 1) ? 1.0 : 0.0;
+    }
+    for (int l = 0; l < m; ++l) {
+        int iter = 0;
+        for (;;) {
+            int mm = l;
+            for (; mm < m - 1; ++mm) {
+                const double dd = fabs(d[mm * G]) + fabs(d[(mm + 1) * G]);
+                if (fabs(e[mm * G]) <= 2.220446049250313e-16 * dd) break;
+            }
+            if (mm == l || iter++ == 100) break;
+            double g = (d[(l + 1) * G] - d[l * G]) / (2.0 * e[l * G]);
+            double r = dev_rot_radius(g, 1.0);
+            g = d[mm * G] - d[l * G] + e[l * G] / (g + copysign(r, g));
+            double s = 1.0, c = 1.0, p = 0.0;
+            bool deflated = false;
+            for (int i = mm - 1; i >= l; --i) {
+                const double f = s * e[i * G], b = c * e[i * G];
+                r = dev_rot_radius(f, g);
+                e[(i + 1) * G] = r;
+                if (r == 0.0) {
+                    d[(i + 1) * G] -= p;
+                    e[mm * G] = 0.0;
+                    deflated = true;
+                    break;
+                }
+                s = f / r;
+                c = g / r;
+                g = d[(i + 1) * G] - p;
+                r = (d[i * G] - g) * s + 2.0 * c * b;
+                p = s * r;
+                d[(i + 1) * G] = g + p;
+                g = c * r - b;
+                const double zf = z[(i + 1) * G];
+                z[(i + 1) * G] = s * z[i * G] + c * zf;
+                z[i * G] = c * z[i * G] - s * zf;
+                if (LAST) {
+                    const double lf = zl[(i + 1) * G];
+                    zl[(i + 1) * G] = s * zl[i * G] + c * lf;
+                    zl[i * G] = c * zl[i * G] - s * lf;
+                }
+            }
+            if (deflated) continue;
+            d[l * G] -= p;
+            e[l * G] = g;
+            e[mm * G] = 0.0;
+        }
+    }
+}
+
+}  // namespace
+
+// The stopping test of the adaptive depth at depth j: one workgroup of one
+// wavefront, lane t owns column c = g0 + t (t < G, c < live).  trec: the
+// sweep's device record [alpha | up | low][mcap][P].  state: kAdaptState
+// doubles per column,
+//   [0] q_j  [1] q_{j-1}  [2] q_{j-2}  [3] depth  [4] stopped  [5] theta_max_j
+//   [6] q_j agreed with q_{j-1}  [7] the depth of the last check
+// (fun = exp: each q scaled by exp(-theta_max) of its own depth).  The two
+// quadrature agreements come from consecutive launches (j - 2, j - 1, j), so
+// a column's decision needs the checks of the two depths before it; a stopped
+// column is left as it is.  Columns < nfe also take the f(A) x residual test
+// (beta_j = low[j-1]).  n2 (nullable): squared column norms, a zero column
+// stops at once with depth 0.  active[0]: the live columns still running, an
+// ordinary store by lane 0 after the barrier.  No cross-lane operation: the
+// lanes' QL loops diverge freely.
+__global__ __launch_bounds__(64) void k_quad_check(const double* __restrict__ trec, int mcap, int P, int j, int live,
+                                                   int g0, int G, int nfe, const double* __restrict__ n2, int fun,
+                                                   double rtol, double* __restrict__ state,
+                                                   int* __restrict__ active) {
+    extern __shared__ double sm[];
+    __shared__ int stopped_l[64];
+    const int t = threadIdx.x, c = g0 + t;
+    const bool mine = t < G && c < live;
+    int stopped = -1;
+    if (mine) {
+        double* st = state + (size_t)c * kAdaptState;
+        stopped = st[4] != 0.0;
+        if (!stopped && n2 && !(n2[c] > 0.0)) {
+            st[0] = 0.0;
+            st[3] = 0.0;
+            st[4] = 1.0;
+            stopped = 1;
+        } else if (!stopped) {
+            const double* al = trec + c;
+            const double* up = trec + (size_t)mcap * P + c;
+            const double* low = trec + (size_t)2 * mcap * P + c;
+            int steps = j;
+            bool broke = false;
+            for (int k = 0; k < j; ++k)
+                if (low[(size_t)k * P] < 1e-8) {
+                    steps = k + 1;
+                    broke = true;
+                    break;
+                }
+            double* d = sm + t;
+            double* e = sm + (size_t)j * G + t;
+            double* z = sm + (size_t)2 * j * G + t;
+            double* zl = sm + (size_t)3 * j * G + t;
+            for (int k = 0; k < steps; ++k) d[k * G] = al[(size_t)k * P];
+            for (int k = 0; k + 1 < steps; ++k) e[k * G] = 0.5 * (low[(size_t)k * P] + up[(size_t)(k + 1) * P]);
+            const bool wf = c < nfe && !broke;
+            if (wf)
+                dev_ql_rows<true>(steps, G, d, e, z, zl);
+            else
+                dev_ql_rows<false>(steps, G, d, e, z, zl);
+            double tm = d[0];
+            for (int k = 1; k < steps; ++k) tm = fmax(tm, d[k * G]);
+            const double shift = (fun == KT_FUN_EXP) ? tm : 0.0;
+            double q = 0.0, lastc = 0.0, nrm2 = 0.0;
+            for (int k = 0; k < steps; ++k) {
+                const double w = dev_fscalar(fun, d[k * G] - shift), z1 = z[k * G];
+                q += z1 * z1 * w;
+                if (wf) lastc += zl[k * G] * z1 * w;
+                nrm2 += z1 * z1 * w * w;
+            }
+            const bool hist = st[7] == (double)(j - 1);
+            const double q1 = st[0];
+            // theta_max grows with the depth: the shallower sum at this depth's scale
+            const double q1s = (fun == KT_FUN_EXP) ? q1 * exp(st[5] - tm) : q1;
+            const bool agree1 = hist && fabs(q - q1s) <= rtol * fabs(q);
+            const bool agree2 = hist && st[6] != 0.0;
+            bool stop = broke;
+            if (!stop && j >= kAdaptMinDepth && agree1 && agree2)
+                stop = !wf || low[(size_t)(j - 1) * P] * fabs(lastc) <= rtol * sqrt(nrm2);
+            st[2] = st[1];
+            st[1] = q1;
+            st[0] = q;
+            st[5] = tm;
+            st[6] = agree1 ? 1.0 : 0.0;
+            st[7] = (double)j;
+            if (stop) {
+                st[3] = (double)steps;
+                st[4] = 1.0;
+                stopped = 1;
+            }
+        }
+    }
+    stopped_l[t] = stopped;
+    __syncthreads();
+    if (t == 0) {
+        int run = 0;
+        for (int k = 0; k < live; ++k) {
+            const bool here = k >= g0 && k < g0 + G;  // another group's columns: an earlier launch wrote them
+            run += here ? (stopped_l[k - g0] == 0) : (state[(size_t)k * kAdaptState + 4] == 0.0);
+        }
+        active[0] = run;
+    }
+}
+
+// P <= 32 columns, 1 <= j <= mcap <= 256.  The four LDS arrays of depth j
+// take 32 j G bytes: every live column in one launch while that fits 64 KB
+// (P = 16 up to depth 128), else column groups of 8 lanes per launch (64 KB
+// at depth 256), each group's count taken over all live columns.
+hipError_t launch_quad_check(const double* trec, int mcap, int P, int j, int live, int nfe, const double* n2,
+                             int fun, double rtol, double* state, int* active, hipStream_t st) {
+    if (P < 1 || P > 32 || live < 1 || live > P || j < 1 || j > mcap || mcap > 256) return hipErrorInvalidValue;
+    const int G = ((size_t)32 * j * P <= (size_t)65536) ? P : 8;
+    for (int g0 = 0; g0 < live; g0 += G) {
+        k_quad_check<<<1, 64, sizeof(double) * 4 * j * G, st>>>(trec, mcap, P, j, live, g0, G, nfe, n2, fun, rtol,
+                                                                 state, active);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// Y[r, c] = sum_{j < m} U_j[r * nc + c] W[j * nc + c], slot j (n x nc,
+// row-major) at tab.chunk[j / spc] + (j % spc) n nc: k_weighted_sum over a
+// basis allocated in growth chunks of spc slots.
+__global__ __launch_bounds__(256) void k_weighted_sum_tab(int n, int m, int nc, SlotTab tab, int spc,
+                                                          const double* __restrict__ W, double* __restrict__ Y,
+                                                          int ldy) {
+    const int64_t total = (int64_t)n * nc;
+    const int64_t sstride = (int64_t)n * nc;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+         t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = t / nc;
+        const int c = (int)(t % nc);
+        double s = 0.0;
+        for (int j = 0; j < m; ++j) {
+            const double* u = tab.chunk[j / spc] + (int64_t)(j % spc) * sstride + t;
+            s = fma(__builtin_nontemporal_load(u), W[j * nc + c], s);
+        }
+        Y[r * ldy + c] = s;
+    }
+}
+
+hipError_t launch_weighted_sum_tab(int n, int m, int nc, const SlotTab& tab, int spc, const double* W, double* Y,
+                                   int ldy, hipStream_t st) {
+    if (spc < 1 || m < 1 || (m + spc - 1) / spc > kSlotTabChunks) return hipErrorInvalidValue;
+    const int64_t total = (int64_t)n * nc;
+    int grid = (int)std::min<int64_t>((total + 255) / 256, 4096);
+    if (grid < 1) grid = 1;
+    k_weighted_sum_tab<<<grid, 256, 0, st>>>(n, m, nc, tab, spc, W, Y, ldy);
+    return hipGetLastError();
+}
+
+}  // namespace kt

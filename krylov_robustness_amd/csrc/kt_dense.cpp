@@ -50,9 +50,14 @@ struct Rot {
 // (The QL iteration is EISPACK IMTQL2's, public domain: Bowdler, Martin,
 // Reinsch & Wilkinson, Numer. Math. 11 (1968); first-row form after Golub &
 // Welsch, Math. Comp. 23 (1969).)
-static void ql_first_row(int m, double* d, double* e, double* z, std::vector<Rot>* log = nullptr) {
+// LAST: the same rotations also carry the last row of Z in zl (the adaptive
+// depth's f(A) x residual test, tridiag_depth_test below).
+template <bool LAST>
+static void ql_rows(int m, double* d, double* e, double* z, double* zl, std::vector<Rot>* log) {
     e[m - 1] = 0.0;
     for (int i = 0; i < m; ++i) z[i] = (i == 0) ? 1.0 : 0.0;
+    if (LAST)
+        for (int i = 0; i < m; ++i) zl[i] = (i == m - 1) ? 1.0 : 0.0;
     for (int l = 0; l < m; ++l) {
         int iter = 0;
         for (;;) {
@@ -87,6 +92,11 @@ static void ql_first_row(int m, double* d, double* e, double* z, std::vector<Rot
                 const double zf = z[i + 1];
                 z[i + 1] = s * z[i] + c * zf;
                 z[i] = c * z[i] - s * zf;
+                if (LAST) {
+                    const double lf = zl[i + 1];
+                    zl[i + 1] = s * zl[i] + c * lf;
+                    zl[i] = c * zl[i] - s * lf;
+                }
                 if (log) log->push_back({i, s, c});
             }
             if (deflated) continue;
@@ -95,6 +105,10 @@ static void ql_first_row(int m, double* d, double* e, double* z, std::vector<Rot
             e[mm] = 0.0;
         }
     }
+}
+
+static void ql_first_row(int m, double* d, double* e, double* z, std::vector<Rot>* log = nullptr) {
+    ql_rows<false>(m, d, e, z, nullptr, log);
 }
 
 double tridiag_quadrature(int m, const double* alpha, const double* off, int fun) {
@@ -131,6 +145,76 @@ double tridiag_fun_e1(int m, const double* alpha, const double* off, int fun, do
         fe1[R.i + 1] = R.c * b - R.s * a;
     }
     return q;
+}
+
+// The sums of the adaptive depth's stopping test on the leading k x k block:
+// theta_max, and with w_i = f(theta_i) (fun = exp: exp(theta_i - theta_max),
+// so a scaled graph does not overflow)
+//   q = sum s_1i^2 w_i,  last = sum s_ki s_1i w_i,  nrm2 = sum s_1i^2 w_i^2.
+static void depth_sums(int k, const double* alpha, const double* off, int fun, bool last, double* tmax, double* q,
+                       double* lastc, double* nrm2) {
+    std::vector<double> d(alpha, alpha + k), e(k, 0.0), z(k), zl(last ? k : 0);
+    for (int i = 0; i + 1 < k; ++i) e[i] = off[i];
+    if (last)
+        ql_rows<true>(k, d.data(), e.data(), z.data(), zl.data(), nullptr);
+    else
+        ql_rows<false>(k, d.data(), e.data(), z.data(), nullptr, nullptr);
+    double tm = d[0];
+    for (int i = 1; i < k; ++i) tm = std::max(tm, d[i]);
+    const double shift = (fun == KT_FUN_EXP) ? tm : 0.0;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int i = 0; i < k; ++i) {
+        const double w = fscalar(fun, d[i] - shift);
+        s0 += z[i] * z[i] * w;
+        if (last) s1 += zl[i] * z[i] * w;
+        s2 += z[i] * z[i] * w * w;
+    }
+    *tmax = tm;
+    *q = s0;
+    *lastc = s1;
+    *nrm2 = s2;
+}
+
+// The adaptive Lanczos depth's stopping test at depth j: the
+// record's first off-diagonal below 1e-8 (the lucky-breakdown cut of
+// record_tridiag) truncates T there and stops the column; otherwise, from
+// depth kAdaptMinDepth on, two consecutive quadrature agreements and, for an
+// f(A) x column, the last component of f(T_j) e1 times beta_j against
+// ||f(T_j) e1||.  off: j - 1 entries, j with want_fe1 (off[j-1] = beta_j).
+DepthTest tridiag_depth_test(int j, const double* alpha, const double* off, int fun, int want_fe1, double rtol) {
+    DepthTest t;
+    const int noff = want_fe1 ? j : j - 1;
+    t.steps = j;
+    for (int k = 0; k < noff; ++k)
+        if (std::fabs(off[k]) < 1e-8) {  // (an oracle's off-diagonals may carry qr's signs)
+            t.steps = k + 1;
+            t.breakdown = true;
+            break;
+        }
+    double tm[3] = {0, 0, 0}, q[3] = {0, 0, 0}, lastc = 0.0, nrm2 = 0.0, dummy0, dummy1;
+    depth_sums(t.steps, alpha, off, fun, want_fe1 && !t.breakdown, &tm[0], &q[0], &lastc, &nrm2);
+    t.q = q[0];
+    t.theta_max = tm[0];
+    if (t.breakdown) {
+        t.converged = true;
+        return t;
+    }
+    if (j < kAdaptMinDepth) return t;
+    for (int b = 1; b <= 2; ++b) {
+        depth_sums(j - b, alpha, off, fun, false, &tm[b], &q[b], &dummy0, &dummy1);
+        // theta_max grows with the depth (interlacing): bring the shallower
+        // sums to depth j's scale
+        if (fun == KT_FUN_EXP) q[b] *= std::exp(tm[b] - tm[0]);
+    }
+    t.r1 = std::fabs(q[0] - q[1]) / std::fabs(q[0]);
+    t.r2 = std::fabs(q[1] - q[2]) / std::fabs(q[1]);
+    bool ok = std::fabs(q[0] - q[1]) <= rtol * std::fabs(q[0]) && std::fabs(q[1] - q[2]) <= rtol * std::fabs(q[1]);
+    if (want_fe1) {
+        t.r3 = std::fabs(off[j - 1] * lastc) / std::sqrt(nrm2);
+        ok = ok && std::fabs(off[j - 1] * lastc) <= rtol * std::sqrt(nrm2);
+    }
+    t.converged = ok;
+    return t;
 }
 
 }  // namespace kt
@@ -481,6 +565,20 @@ extern "C" int kt_host_tridiag_quad(int m, const double* alpha, const double* of
         return KT_ERR_ARG;
     }
     *q = fe1 ? kt::tridiag_fun_e1(m, alpha, off, fun, fe1) : kt::tridiag_quadrature(m, alpha, off, fun);
+    return KT_OK;
+}
+
+extern "C" int kt_host_quad_converged(int j, const double* alpha, const double* off, int fun, int want_fe1,
+                                      double rtol, int* converged, double* q) {
+    if (j < 1 || j > kt::kAdaptMaxCap || !alpha || ((j > 1 || want_fe1) && !off) || !converged || !q ||
+        fun < KT_FUN_EXP || fun > KT_FUN_SQRT) {
+        kt::set_error("kt_host_quad_converged: bad argument (1 <= j <= 256, non-NULL arrays and outputs)");
+        return KT_ERR_ARG;
+    }
+    const kt::DepthTest t =
+        kt::tridiag_depth_test(j, alpha, off, fun, want_fe1 != 0, rtol > 0.0 ? rtol : kt::kAdaptRtol);
+    *converged = t.converged ? 1 : 0;
+    *q = t.q;
     return KT_OK;
 }
 

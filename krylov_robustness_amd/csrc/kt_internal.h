@@ -1,6 +1,7 @@
 // kt_internal.h -- shared internals of libkrylov_hip.so (not part of the ABI).
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -213,6 +214,12 @@ struct Workspace {
     PinnedBuf pin_colrec;
     DevBuf colnorm;  // the block's squared column norms (device)
     hipEvent_t colsplit_ev = nullptr;
+    // lanczos_columns_adaptive (kt_slq.cpp): per sweep lane the depth check's
+    // device block (kt_adapt.hip: 8 doubles per column, then the count of
+    // still-active columns), the pinned words the host polls and their events
+    DevBuf adapt_state[4];
+    PinnedBuf pin_adapt;
+    hipEvent_t adapt_ev[4][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
 };
 
 }  // namespace kt
@@ -232,6 +239,8 @@ struct kt_context_s {
     int64_t fu_last_cols = 0;  // projected size of the last fun_update (n when dense)
     int64_t expmv_calls = 0;   // expmv_device calls (kt_expmv and the expmv Afun of mc_trace)
     int64_t expmv_terms = 0;   // Taylor terms those calls executed (one A b product each, expmv.m:75)
+    int64_t adapt_max_depth = 0;  // adaptive Lanczos Afun: the largest depth a column used
+    int64_t adapt_capped = 0;     // ... and its columns that reached the depth cap unconverged
     int ky_flags = 8;   // y-form pass flags (8 = nontemporal store of y_{j+1}, +0.3 %)
     bool yform = true;  // KT_SLQ_YFORM=0: the hot path runs the explicit K1/K2 sweep
     void* blas = nullptr;  // rocblas_handle, created on first block-Krylov use
@@ -361,6 +370,22 @@ double fscalar(int fun, double x);
 double tridiag_quadrature(int m, const double* alpha, const double* off, int fun);
 // The same quadrature, and f(T) e1 into fe1[0..m-1], from one QL pass.
 double tridiag_fun_e1(int m, const double* alpha, const double* off, int fun, double* fe1);
+// The adaptive Lanczos depth (KT_AFUN_LANCZOS_AUTO, kt_lanczos_fmv_auto):
+// the first depth tested, the depth cap's default and ceiling, and the default
+// rtol (ten times the smallest power of ten at which every column of the
+// measured graphs stops before depth 128, profiles/adaptive/rtol_sweep.txt).
+constexpr int kAdaptMinDepth = 8;
+constexpr int kAdaptDefaultCap = 128;
+constexpr int kAdaptMaxCap = 256;
+constexpr double kAdaptRtol = 1e-12;
+struct DepthTest {
+    bool converged = false, breakdown = false;
+    int steps = 0;           // rows of T the sums were formed on (the breakdown cut)
+    double q = 0.0;          // e1' f(T) e1 (fun = exp: times exp(-theta_max))
+    double theta_max = 0.0;
+    double r1 = INFINITY, r2 = INFINITY, r3 = 0.0;  // the test's three ratios (each against rtol)
+};
+DepthTest tridiag_depth_test(int j, const double* alpha, const double* off, int fun, int want_fe1, double rtol);
 bool chol_upper(double* G, int n);
 void tri_upper_inv(const double* R, int n, double* X);
 void sym_eig_host(int n, const double* A, double* w, double* V);

@@ -113,6 +113,20 @@ hipError_t launch_spmm_lanczos_start(int P, int flags, int grid, const int* rp, 
 hipError_t launch_ycoef(int P, const double* partial, int nblk, int start, int last, double s0,
                         double* ys, double* t_alpha, double* t_up, double* t_low, double* guard,
                         hipStream_t st);
+// the adaptive Lanczos depth (kt_adapt.hip): the stopping test at depth j on a
+// sweep's device record [alpha | up | low][mcap][P] (state: kAdaptState
+// doubles per column, zeroed before the sweep's first check; the checks of a
+// sweep run at consecutive depths), and k_weighted_sum over a basis kept in
+// chunks of spc slots (slot j: n x nc row-major)
+constexpr int kAdaptState = 8;
+constexpr int kSlotTabChunks = 8;
+struct SlotTab {
+    const double* chunk[kSlotTabChunks];
+};
+hipError_t launch_quad_check(const double* trec, int mcap, int P, int j, int live, int nfe, const double* n2,
+                             int fun, double rtol, double* state, int* active, hipStream_t st);
+hipError_t launch_weighted_sum_tab(int n, int m, int nc, const SlotTab& tab, int spc, const double* W, double* Y,
+                                   int ldy, hipStream_t st);
 hipError_t launch_fill(double* x, int count, double v, hipStream_t st);
 hipError_t launch_delay(double microseconds, hipStream_t st);
 // sweep start scales from device column norms (kt_slq.cpp; mode 0 explicit: sc,

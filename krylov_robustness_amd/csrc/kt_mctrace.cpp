@@ -51,7 +51,7 @@ static const double kTheta[100] = {
 21.300519898663481, 21.576378150721375, 21.85232495499011, 22.128357353464594
 };
 
-enum { AFUN_MATRIX = 0, AFUN_LANCZOS = 1, AFUN_EXPMV = 2 };
+enum { AFUN_MATRIX = 0, AFUN_LANCZOS = 1, AFUN_EXPMV = 2, AFUN_LANCZOS_AUTO = 3 };
 
 // B = A - mu I (expmv.m:33-36 shift; A symmetric, so B' = B): y = B x on one
 // column, as the SpMV of A followed by y -= mu x.
@@ -426,6 +426,8 @@ struct AfunDev {
         switch (kind) {
         case AFUN_MATRIX: spmm(A, X, ld, Y, ld, nc); break;
         case AFUN_LANCZOS: lanczos_columns(A, X, ld, nc, m, fun, nullptr, Y, ld); break;
+        // m is the depth cap; a capped column is counted (kt_context_stat 6), not an error
+        case AFUN_LANCZOS_AUTO: lanczos_columns_adaptive(A, X, ld, nc, nc, m, 0.0, fun, nullptr, Y, ld); break;
         default: expmv_device(A, 1.0, X, ld, nc, Y); break;
         }
     }
@@ -433,6 +435,10 @@ struct AfunDev {
     void quad_cols(const double* X, int ld, int nc, double* q) {
         if (kind == AFUN_LANCZOS) {
             lanczos_columns(A, X, ld, nc, m, fun, q, nullptr, 0);
+            return;
+        }
+        if (kind == AFUN_LANCZOS_AUTO) {
+            lanczos_columns_adaptive(A, X, ld, nc, 0, m, 0.0, fun, q, nullptr, 0);
             return;
         }
         DevMat Y;
@@ -649,7 +655,10 @@ void mc_trace_impl(kt_matrix_s* A, AfunDev& F, double tol, int maxit, int isArea
     const bool sharded = sh.allreduce != nullptr && F.kind != AFUN_EXPMV;
     const char* se = getenv("KT_MC_SPEC");
     kt_matrix_s* A3 = nullptr;  // the speculative S terms' matrix
-    if (!sharded && K > 1 && !(se && se[0] == '0')) {
+    // the adaptive Lanczos kind runs in the serial order on A alone (no twin,
+    // no speculative S term): its depth statistics live on A's context
+    const bool serial = F.kind == AFUN_LANCZOS_AUTO;
+    if (!sharded && !serial && K > 1 && !(se && se[0] == '0')) {
         kt_matrix_s* A2 = twin_of(A);
         if (A2) A3 = twin_of(A2);
     }
@@ -701,7 +710,7 @@ void mc_trace_impl(kt_matrix_s* A, AfunDev& F, double tol, int maxit, int isArea
         // tr += trace(Q' Afun_it(Q)) = sum quadforms of P_1..P_{it-1} Q          :46
         copy_cols(ctx, n, Yc, ld, Z.col(0), ld, mb);
         for (int q = (int)Qs.size() - 1; q >= 0; --q) project(ctx, n, Qs[q].col(0), ld, mb, Z.col(0), mb);
-        const bool split = !sharded;  // the G term is local
+        const bool split = !sharded && !serial;  // the G term is local
         kt_matrix_s* A2 = split ? twin_of(A) : nullptr;
         if (!A2) tr += F.trace_quad(Z.col(0), ld, mb);
         Qs.emplace_back();                                                         // :47-48
@@ -779,7 +788,20 @@ void mc_trace_impl(kt_matrix_s* A, AfunDev& F, double tol, int maxit, int isArea
         } else if (sharded) {
             std::vector<double> qv(mb, 0.0), qm;
             int nm = 0;
-            for (int c = sh.rank; c < mb; c += sh.world) copy_cols(ctx, n, Z.col(c), ld, Yc + nm++, ld, 1);
+            if (serial) {
+                // the adaptive kind keeps G column c in slot c at every world
+                // size (the other ranks' columns zeroed: a zero column stops at
+                // once with form 0), so a column's sweep never depends on the
+                // rank count
+                copy_cols(ctx, n, Z.col(0), ld, Yc, ld, mb);
+                for (int c = 0; c < mb; ++c)
+                    if (c % sh.world != sh.rank) zero_cols(ctx, n, Yc + c, ld, 1);
+                qm.assign(mb, 0.0);
+                F.quad_cols(Yc, ld, mb, qm.data());
+                for (int c = sh.rank; c < mb; c += sh.world) qv[c] = qm[c];
+            } else {
+                for (int c = sh.rank; c < mb; c += sh.world) copy_cols(ctx, n, Z.col(c), ld, Yc + nm++, ld, 1);
+            }
             if (nm > 0) {
                 zero_cols(ctx, n, Yc + nm, ld, ld - nm);
                 qm.assign(nm, 0.0);
@@ -826,9 +848,10 @@ int kt_mc_trace(kt_matrix_t A, int afun, int fun, int m, double tol, int maxit, 
                 uint64_t seed, double* tr, double* res, int* it) {
     KT_TRY
     if (!A || !tr) fail(KT_ERR_ARG, "NULL argument");
-    if (afun < AFUN_MATRIX || afun > AFUN_EXPMV) fail(KT_ERR_ARG, "unknown Afun kind");
+    if (afun < AFUN_MATRIX || afun > AFUN_LANCZOS_AUTO) fail(KT_ERR_ARG, "unknown Afun kind");
     if (fun < KT_FUN_EXP || fun > KT_FUN_SQRT) fail(KT_ERR_ARG, "unknown fun code");
     if (afun == AFUN_LANCZOS && (m < 1 || m > 256)) fail(KT_ERR_ARG, "m must be in [1, 256]");
+    if (afun == AFUN_LANCZOS_AUTO && m > kAdaptMaxCap) fail(KT_ERR_ARG, "the Lanczos depth cap must be at most 256");
     if (maxit < 1) fail(KT_ERR_ARG, "maxit must be >= 1");
     if (A->n < 10) fail(KT_ERR_UNSUPPORTED, "mc_trace needs n >= 10 (qr of an n x 10 block)");
     KT_HIP(hipSetDevice(A->ctx->device));
@@ -844,9 +867,10 @@ int kt_mc_trace_sharded(kt_matrix_t A, int afun, int fun, int m, double tol, int
     if (!A || !tr) fail(KT_ERR_ARG, "NULL argument");
     if (world < 1 || rank < 0 || rank >= world) fail(KT_ERR_ARG, "bad rank / world");
     if (world > 1 && !allreduce) fail(KT_ERR_ARG, "world > 1 needs an all-reduce callback");
-    if (afun < AFUN_MATRIX || afun > AFUN_EXPMV) fail(KT_ERR_ARG, "unknown Afun kind");
+    if (afun < AFUN_MATRIX || afun > AFUN_LANCZOS_AUTO) fail(KT_ERR_ARG, "unknown Afun kind");
     if (fun < KT_FUN_EXP || fun > KT_FUN_SQRT) fail(KT_ERR_ARG, "unknown fun code");
     if (afun == AFUN_LANCZOS && (m < 1 || m > 256)) fail(KT_ERR_ARG, "m must be in [1, 256]");
+    if (afun == AFUN_LANCZOS_AUTO && m > kAdaptMaxCap) fail(KT_ERR_ARG, "the Lanczos depth cap must be at most 256");
     if (maxit < 1) fail(KT_ERR_ARG, "maxit must be >= 1");
     if (A->n < 10) fail(KT_ERR_UNSUPPORTED, "mc_trace needs n >= 10 (qr of an n x 10 block)");
     KT_HIP(hipSetDevice(A->ctx->device));
@@ -859,7 +883,9 @@ int kt_mc_trace_sharded(kt_matrix_t A, int afun, int fun, int m, double tol, int
 int kt_trace_exp(kt_matrix_t A, int afun, int m, uint64_t seed, double* tr) {
     KT_TRY
     if (!A || !tr) fail(KT_ERR_ARG, "NULL argument");
-    if (afun != AFUN_LANCZOS && afun != AFUN_EXPMV) fail(KT_ERR_ARG, "trace_exp: Afun must be Lanczos or expmv");
+    if (afun != AFUN_LANCZOS && afun != AFUN_EXPMV && afun != AFUN_LANCZOS_AUTO)
+        fail(KT_ERR_ARG, "trace_exp: Afun must be Lanczos or expmv");
+    if (afun == AFUN_LANCZOS_AUTO && m > kAdaptMaxCap) fail(KT_ERR_ARG, "the Lanczos depth cap must be at most 256");
     if (A->n < 10) fail(KT_ERR_UNSUPPORTED, "trace_exp needs n >= 10");
     KT_HIP(hipSetDevice(A->ctx->device));
     AfunDev F{A, afun, KT_FUN_EXP, m};
@@ -898,6 +924,26 @@ int kt_lanczos_fmv(kt_matrix_t A, int fun, int m, int64_t ncols, const double* X
     upload_rows(A, X, (int)ncols, Xd.col(0), ld);
     lanczos_columns(A, Xd.col(0), ld, (int)ncols, m, fun, nullptr, Yd.col(0), ld);
     download_block(A, Yd.col(0), ld, (int)ncols, Y);
+    KT_CATCH
+}
+
+int kt_lanczos_fmv_auto(kt_matrix_t A, int fun, int m_max, double rtol, int64_t ncols, const double* X,
+                        double* Y, double* quad, int* depth, int* capped) {
+    KT_TRY
+    if (!A || !X || (!Y && !quad) || ncols < 1 || ncols > 128)
+        fail(KT_ERR_ARG, "bad argument (1 <= ncols <= 128, Y or quad required)");
+    if (fun < KT_FUN_EXP || fun > KT_FUN_SQRT) fail(KT_ERR_ARG, "unknown fun code");
+    if (m_max > kAdaptMaxCap) fail(KT_ERR_ARG, "the Lanczos depth cap must be at most 256");
+    KT_HIP(hipSetDevice(A->ctx->device));
+    const int ld = pow2_at_least((int)ncols);
+    DevMat Xd, Yd;
+    Xd.alloc(A->ctx, A->n, ld);
+    if (Y) Yd.alloc(A->ctx, A->n, ld);
+    upload_rows(A, X, (int)ncols, Xd.col(0), ld);
+    const int nc = lanczos_columns_adaptive(A, Xd.col(0), ld, (int)ncols, Y ? (int)ncols : 0, m_max, rtol, fun, quad,
+                                            Y ? Yd.col(0) : nullptr, ld, depth);
+    if (Y) download_block(A, Yd.col(0), ld, (int)ncols, Y);
+    if (capped) *capped = nc;
     KT_CATCH
 }
 

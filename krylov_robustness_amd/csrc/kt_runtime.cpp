@@ -458,6 +458,9 @@ int kt_context_destroy(kt_context_t ctx) {
     if (w.qrfac_ev) (void)hipEventDestroy(w.qrfac_ev);
     if (w.qrm_ev) (void)hipEventDestroy(w.qrm_ev);
     if (w.colsplit_ev) (void)hipEventDestroy(w.colsplit_ev);
+    for (auto& lane : w.adapt_ev)
+        for (auto& e : lane)
+            if (e) (void)hipEventDestroy(e);
     for (auto& b : w.host_trec) b.release();
     for (auto& pd : w.slq_pend)
         for (auto& e : pd.done)
@@ -597,9 +600,9 @@ int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* tot
 
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value) {
     KT_GUARD_BEGIN
-    if (!ctx || !value || stat < 0 || stat > 4) fail(KT_ERR_ARG, "bad stat query");
-    const int64_t v[5] = {ctx->yform_redone, ctx->fu_dense, ctx->fu_last_cols, ctx->expmv_calls,
-                          ctx->expmv_terms};
+    if (!ctx || !value || stat < 0 || stat > 6) fail(KT_ERR_ARG, "bad stat query");
+    const int64_t v[7] = {ctx->yform_redone, ctx->fu_dense, ctx->fu_last_cols, ctx->expmv_calls,
+                          ctx->expmv_terms, ctx->adapt_max_depth, ctx->adapt_capped};
     *value = v[stat];
     KT_GUARD_END
 }

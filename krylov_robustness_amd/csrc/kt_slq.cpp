@@ -110,11 +110,28 @@ void ExplicitSweep::start() {
     bbase = basis ? basis->col(0) : nullptr;
 }
 
+void ExplicitSweep::use_basis_chunks(std::vector<DevMat>* chunks_, int spc_) {
+    chunks = chunks_;
+    spc = spc_;
+}
+
+// basis slot j (nullptr: the sweep keeps no basis)
+double* ExplicitSweep::slot(int j) {
+    if (chunks) {
+        const size_t k = (size_t)(j / spc);
+        if (chunks->size() <= k) chunks->resize(k + 1);
+        DevMat& cm = (*chunks)[k];
+        if (!cm.ptr) cm.alloc(A->ctx, n, spc * bcols, false);  // every slot used is written by the sweep
+        return cm.col(0) + (size_t)(j % spc) * n * bcols;
+    }
+    return bbase ? bbase + (size_t)j * n * bcols : nullptr;
+}
+
 void ExplicitSweep::step(int j) {
     kt_context_s* ctx = A->ctx;
     const int first = (j == 0);
-    if (basis && first)  // u_0 into slot 0
-        KT_HIP(hipMemcpy2DAsync(bbase, sizeof(double) * bcols, ucur, sizeof(double) * P, sizeof(double) * bcols,
+    if ((basis || chunks) && first)  // u_0 into slot 0
+        KT_HIP(hipMemcpy2DAsync(slot(0), sizeof(double) * bcols, ucur, sizeof(double) * P, sizeof(double) * bcols,
                                 (size_t)n, hipMemcpyDeviceToDevice, st));
     prof_begin(ctx, PROF_SPMM, st, P);
     KT_HIP(launch_spmm_dot(P, ctx->k1_flags | (A->unit_values ? 2 : 0), grid1, M.rowptr, M.col, M.val, n, ucur, sc, Yb,
@@ -125,7 +142,7 @@ void ExplicitSweep::step(int j) {
                             trec + (size_t)(1 * m + j) * P, hist_dev ? hist_dev->as<double>() + (size_t)j * P : nullptr,
                             st));
     prof_begin(ctx, PROF_UPDATE, st, P);
-    double* rec = (basis && j + 1 < m) ? bbase + (size_t)(j + 1) * n * bcols : nullptr;
+    double* rec = ((basis || chunks) && j + 1 < m) ? slot(j + 1) : nullptr;
     KT_HIP(launch_update(P, grid, n, Yb, uprev, ucur, sc, sp, coef, first, part2, st, ctx->k2_nt, rec, bcols));
     prof_end(ctx, PROF_UPDATE, st);
     KT_HIP(launch_norm(P, part2, grid, k2s, sn, trec + (size_t)(2 * m + j) * P, st));
@@ -140,6 +157,16 @@ void ExplicitSweep::finish() {
     KT_HIP(hipMemcpyAsync(rec_host, trec, sizeof(double) * (size_t)3 * m * P, hipMemcpyDeviceToHost, st));
     if (scale_hist)
         KT_HIP(hipMemcpyAsync(scale_hist->data(), hist_dev->ptr, sizeof(double) * (size_t)m * P,
+                              hipMemcpyDeviceToHost, st));
+}
+
+void ExplicitSweep::finish(int rows) {
+    if (rows <= 0) return;
+    // the three record blocks' first `rows` rows, at the capacity's stride
+    KT_HIP(hipMemcpy2DAsync(rec_host, sizeof(double) * (size_t)m * P, trec, sizeof(double) * (size_t)m * P,
+                            sizeof(double) * (size_t)rows * P, 3, hipMemcpyDeviceToHost, st));
+    if (scale_hist)
+        KT_HIP(hipMemcpyAsync(scale_hist->data(), hist_dev->ptr, sizeof(double) * (size_t)rows * P,
                               hipMemcpyDeviceToHost, st));
 }
 
@@ -608,6 +635,221 @@ void lanczos_columns_split(kt_matrix_s* A, const double* X, int ldx, int ncols, 
         }
     }
     if (perm && ny) KT_HIP(launch_perm_rows((int)n, ny, perm, 0, Ys, ldys, Y, ldy, ctx->stream));
+}
+
+// Column c of a record with row capacity mcap, truncated at depth d: the
+// tridiagonal record_tridiag forms from a d-row record.
+static int record_tridiag_at(const double* R, int mcap, int d, int P, int c, double* al, double* off) {
+    int steps = d;
+    for (int j = 0; j < d; ++j)
+        if (R[(size_t)(2 * mcap + j) * P + c] < 1e-8) {
+            steps = j + 1;
+            break;
+        }
+    for (int j = 0; j < steps; ++j) al[j] = R[(size_t)(0 * mcap + j) * P + c];
+    for (int j = 0; j + 1 < steps; ++j)
+        off[j] = 0.5 * (R[(size_t)(2 * mcap + j) * P + c] + R[(size_t)(1 * mcap + j + 1) * P + c]);
+    return steps;
+}
+
+// The adaptive depth.  Sweeps are always kAdaptP wide, so a
+// column's recurrence does not depend on how many columns the call has; its
+// depth is decided on the device from its own record and its values formed
+// from that record truncated there.  The check of depth j + 1 is queued
+// behind step j; every kAdaptPoll steps the sweep's count of running columns
+// is copied to a pinned word behind an event, and the host reads the copy of
+// the poll before (so kAdaptPoll steps stay queued) and stops queueing the
+// sweep once it reads 0.  Steps queued past a column's depth are harmless.
+// The f(A) x columns' basis grows in chunks of kAdaptSlots slots.
+constexpr int kAdaptP = 16, kAdaptPoll = 4, kAdaptSlots = 32;
+
+int lanczos_columns_adaptive(kt_matrix_s* A, const double* X, int ldx, int ncols, int ny, int m_max, double rtol,
+                             int fun, double* quad, double* Y, int ldy, int* depth) {
+    kt_context_s* ctx = A->ctx;
+    const int64_t n = A->n;
+    if (!Y) ny = 0;
+    if (ncols < 1 || ny < 0 || ny > ncols) fail(KT_ERR_ARG, "lanczos_columns_adaptive: 0 <= ny <= ncols, ncols >= 1");
+    if (m_max <= 0) m_max = kAdaptDefaultCap;
+    if (m_max > kAdaptMaxCap) fail(KT_ERR_ARG, "the Lanczos depth cap must be at most 256");
+    if (!(rtol > 0.0)) rtol = kAdaptRtol;
+    const int m = m_max, P = kAdaptP;
+    ctx->ws.colnorm.ensure(sizeof(double) * ncols);
+    double* dn2 = ctx->ws.colnorm.as<double>();
+    KT_HIP(launch_gram_diag(gram_device(ctx, n, X, ldx, ncols, X, ldx, ncols), ncols, ncols, dn2, ctx->stream));
+    // the hubs-first CSR, the block permuted in and f(A) x back out, as
+    // lanczos_columns_split does
+    const DevCSR& M = hub_csr(A);
+    const int* perm = M.perm;
+    DevMat Xh, Yh;
+    const double* Xs = X;
+    int ldxs = ldx;
+    double* Ys = Y;
+    int ldys = ldy;
+    if (perm) {
+        Xh.alloc(ctx, n, ncols, false);
+        KT_HIP(launch_perm_rows((int)n, ncols, perm, 1, X, ldx, Xh.col(0), ncols, ctx->stream));
+        Xs = Xh.col(0);
+        ldxs = ncols;
+        if (ny) {
+            Yh.alloc(ctx, n, ny, false);
+            Ys = Yh.col(0);
+            ldys = ny;
+        }
+    }
+    const int nsw = (ncols + P - 1) / P;
+    const size_t rec = (size_t)3 * m * P, stw = (size_t)P * kAdaptState;
+    // pinned: per sweep its record and state block, then the norms
+    PinnedBuf& hr = ctx->ws.pin_colrec;
+    hr.ensure(sizeof(double) * ((rec + stw) * nsw + ncols));
+    double* hn2 = hr.as<double>() + (rec + stw) * nsw;
+    KT_HIP(hipMemcpyAsync(hn2, dn2, sizeof(double) * ncols, hipMemcpyDeviceToHost, ctx->stream));
+    PinnedBuf& pw = ctx->ws.pin_adapt;  // the polled words: [lane][2]
+    pw.ensure(sizeof(int) * 8);
+    volatile int* polled = pw.as<int>();
+    hipEvent_t ready = ctx->ws.colsplit_ev;
+    if (!ready) {
+        KT_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+        ctx->ws.colsplit_ev = ready;
+    }
+    KT_HIP(hipEventRecord(ready, ctx->stream));
+    const int lanes = std::min(4, nsw);
+    for (int l = 0; l < lanes; ++l) {
+        if (l) {
+            hipStream_t& as = ctx->aux_stream[l - 1];
+            if (!as) KT_HIP(hipStreamCreateWithFlags(&as, hipStreamNonBlocking));
+            KT_HIP(hipStreamWaitEvent(as, ready, 0));
+        }
+        for (auto& e : ctx->ws.adapt_ev[l])
+            if (!e) KT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        ctx->ws.adapt_state[l].ensure(sizeof(double) * (stw + 1));
+    }
+    std::vector<std::vector<DevMat>> bases(nsw);  // per sweep: the basis chunks of its f(A) x columns
+    std::vector<std::vector<double>> hists(nsw);
+    std::vector<int> rows(nsw, 0);                // record rows written per sweep
+    // one sweep per lane at a time, the lanes' sweeps queued step by step
+    for (int s0 = 0; s0 < nsw; s0 += lanes) {
+        const int g = std::min(lanes, nsw - s0);
+        std::vector<std::unique_ptr<ExplicitSweep>> ex;
+        std::vector<char> done(g, 0);
+        for (int l = 0; l < g; ++l) {
+            const int i = s0 + l, c0 = i * P, nc = std::min(P, ncols - c0);
+            const int nyc = std::max(0, std::min(nc, ny - c0));
+            double* R = hr.as<double>() + (rec + stw) * i;
+            ex.emplace_back(new ExplicitSweep(A, M, P, m, 0, 0, Xs + c0, ldxs, nc, dn2 + c0, R, nullptr,
+                                              nyc ? &hists[i] : nullptr, l, nyc));
+            if (nyc) ex.back()->use_basis_chunks(&bases[i], kAdaptSlots);
+            KT_HIP(hipMemsetAsync(ctx->ws.adapt_state[l].ptr, 0, sizeof(double) * (stw + 1), ex.back()->stream()));
+            polled[2 * l] = polled[2 * l + 1] = 1;
+        }
+        for (auto& e : ex) e->start();
+        int npoll = 0;
+        for (int j = 0; j < m; ++j) {
+            bool any = false;
+            for (int l = 0; l < g; ++l) {
+                if (done[l]) continue;
+                any = true;
+                const int i = s0 + l, c0 = i * P, nc = std::min(P, ncols - c0);
+                const int nyc = std::max(0, std::min(nc, ny - c0));
+                ExplicitSweep& e = *ex[l];
+                e.step(j);
+                rows[i] = j + 1;
+                double* dst = ctx->ws.adapt_state[l].as<double>();
+                int* dact = reinterpret_cast<int*>(dst + stw);
+                // checks from two depths before the first decision (its two agreements)
+                if (j + 1 >= kAdaptMinDepth - 2)
+                    KT_HIP(launch_quad_check(e.device_record(), m, P, j + 1, nc, nyc, dn2 + c0, fun, rtol, dst, dact,
+                                             e.stream()));
+                if (j + 1 >= kAdaptMinDepth && (j + 1) % kAdaptPoll == 0) {
+                    int* word = const_cast<int*>(polled) + 2 * l + (npoll & 1);
+                    KT_HIP(hipMemcpyAsync(word, dact, sizeof(int), hipMemcpyDeviceToHost, e.stream()));
+                    KT_HIP(hipEventRecord(ctx->ws.adapt_ev[l][npoll & 1], e.stream()));
+                }
+            }
+            if (!any) break;
+            if (j + 1 >= kAdaptMinDepth && (j + 1) % kAdaptPoll == 0) {
+                // the poll before this one: its event has kAdaptPoll steps queued behind it
+                if (npoll > 0)
+                    for (int l = 0; l < g; ++l) {
+                        if (done[l]) continue;
+                        KT_HIP(hipEventSynchronize(ctx->ws.adapt_ev[l][(npoll - 1) & 1]));
+                        if (polled[2 * l + ((npoll - 1) & 1)] == 0) done[l] = 1;
+                    }
+                ++npoll;
+            }
+        }
+        for (int l = 0; l < g; ++l) {
+            const int i = s0 + l;
+            ex[l]->finish(rows[i]);
+            KT_HIP(hipMemcpyAsync(hr.as<double>() + (rec + stw) * i + rec, ctx->ws.adapt_state[l].ptr,
+                                  sizeof(double) * stw, hipMemcpyDeviceToHost, ex[l]->stream()));
+        }
+        // the lanes' buffers and state blocks are reused by the next group
+        KT_HIP(hipStreamSynchronize(ctx->stream));
+        for (int l = 1; l < g; ++l) KT_HIP(hipStreamSynchronize(ctx->aux_stream[l - 1]));
+    }
+    KT_HIP(hipStreamSynchronize(ctx->stream));
+    const std::vector<double> norms2(hn2, hn2 + ncols);
+    // per column on the host pool, at its own depth: the quadrature and, for
+    // the f(A) x columns, f(T) e1 -> the basis weights
+    std::vector<int> dep(ncols, 0);
+    std::vector<char> cap(ncols, 0);
+    std::vector<std::vector<double>> Ws(nsw);
+    std::vector<int> nycs(nsw, 0);
+    for (int i = 0; i < nsw; ++i) {
+        const int c0 = i * P, nc = std::min(P, ncols - c0);
+        nycs[i] = std::max(0, std::min(nc, ny - c0));
+        Ws[i].assign((size_t)m * std::max(nycs[i], 1), 0.0);
+    }
+    HostPool::get().run(ncols, [&](int t) {
+        const int i = t / P, c = t % P, nyc = nycs[i];
+        const double* R = hr.as<double>() + (rec + stw) * i;
+        const double* st = R + rec + (size_t)c * kAdaptState;
+        if (norms2[t] == 0.0) {
+            if (quad) quad[t] = 0.0;
+            return;
+        }
+        // a column the device did not stop ran every row the sweep wrote
+        const bool stopped = st[4] != 0.0;
+        const int d = stopped ? (int)st[3] : rows[i];
+        std::vector<double> al(d), off(d), fe1(d);
+        const int steps = record_tridiag_at(R, m, d, P, c, al.data(), off.data());
+        // unconverged at the cap, unless the record's last row is a lucky breakdown
+        cap[t] = !stopped && !(R[(size_t)(2 * m + steps - 1) * P + c] < 1e-8);
+        dep[t] = steps;
+        if (c >= nyc) {
+            if (quad) quad[t] = norms2[t] * tridiag_quadrature(steps, al.data(), off.data(), fun);
+            return;
+        }
+        const double qd = tridiag_fun_e1(steps, al.data(), off.data(), fun, fe1.data());
+        if (quad) quad[t] = norms2[t] * qd;
+        const double nx = std::sqrt(norms2[t]);
+        for (int j = 0; j < steps; ++j)
+            Ws[i][(size_t)j * nyc + c] = nx * hists[i][(size_t)j * P + c] * fe1[j];  // v_j = s_j u_j
+    }, 4);
+    for (int i = 0; i < nsw; ++i) {
+        const int nyc = nycs[i], c0 = i * P;
+        if (!nyc) continue;
+        int mt = 1;
+        for (int c = 0; c < nyc; ++c) mt = std::max(mt, dep[c0 + c]);
+        SlotTab tab{};
+        for (size_t k = 0; k < bases[i].size() && k < (size_t)kSlotTabChunks; ++k) tab.chunk[k] = bases[i][k].col(0);
+        DevBuf& dw = ctx->ws.small2;
+        dw.ensure(sizeof(double) * Ws[i].size());
+        KT_HIP(hipMemcpyAsync(dw.ptr, Ws[i].data(), sizeof(double) * (size_t)mt * nyc, hipMemcpyHostToDevice,
+                              ctx->stream));
+        KT_HIP(launch_weighted_sum_tab((int)n, mt, nyc, tab, kAdaptSlots, dw.as<double>(), Ys + c0, ldys, ctx->stream));
+        KT_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    if (perm && ny) KT_HIP(launch_perm_rows((int)n, ny, perm, 0, Ys, ldys, Y, ldy, ctx->stream));
+    int ncap = 0, dmax = 0;
+    for (int t = 0; t < ncols; ++t) {
+        ncap += cap[t];
+        dmax = std::max(dmax, dep[t]);
+        if (depth) depth[t] = dep[t];
+    }
+    ctx->adapt_max_depth = std::max<int64_t>(ctx->adapt_max_depth, dmax);
+    ctx->adapt_capped += ncap;
+    return ncap;
 }
 
 static bool pow2_le128(int b) { return b >= 1 && b <= 128 && (b & (b - 1)) == 0; }

@@ -27,8 +27,22 @@ class ExplicitSweep {
     void start();
     void step(int j);
     void finish();
+    // The resumable form (lanczos_columns_adaptive): a sweep constructed with
+    // capacity m (record rows, scale history, basis slots) runs step(j) only
+    // as far as needed; finish(rows) copies the rows written.  The basis of
+    // its first bcols columns may live in growth chunks of `spc` slots each
+    // (slot j in (*chunks)[j / spc], allocated when step j - 1 is queued)
+    // instead of one m-slot block: pass basis = nullptr and call this before
+    // start().
+    void use_basis_chunks(std::vector<DevMat>* chunks, int spc);
+    void finish(int rows);
+    const double* device_record() const { return trec; }
+    hipStream_t stream() const { return st; }
 
    private:
+    double* slot(int j);
+    std::vector<DevMat>* chunks = nullptr;
+    int spc = 0;
     kt_matrix_s* A;
     const DevCSR& M;
     int P, m;
@@ -136,6 +150,20 @@ void lanczos_columns(kt_matrix_s* A, const double* X, int ldx, int ncols, int m,
 // basis sweep whose guard trips is redone whole by the explicit sweep.
 void lanczos_columns_split(kt_matrix_s* A, const double* X, int ldx, int ncols, int ny, int ne, int m, int fun,
                            double* quad, double* Y, int ldy, int px = 0, int ychunk = 16, int yb = 0);
+
+// lanczos_columns_split's column contract (the first ny columns need f(A) x
+// into Y, every column its quadratic form) with the depth chosen per column:
+// every column by explicit CGS2 sweeps, always 16 wide, each step followed by
+// the device stopping test (kt_adapt.hip k_quad_check); a sweep is queued
+// until its columns have all stopped or reached m_max (<= 0: 128; <= 256).
+// A column's values come from its record truncated at its own depth, by the
+// host quadrature lanczos_columns_split uses, so they do not depend on the
+// columns it shares a sweep or a call with.  rtol <= 0: kAdaptRtol.
+// depth (ncols, nullable): steps used per column (0 for a zero column).
+// Returns the number of columns that reached m_max unconverged; the
+// context's stats (kt_context_stat 5, 6) follow.
+int lanczos_columns_adaptive(kt_matrix_s* A, const double* X, int ldx, int ncols, int ny, int m_max, double rtol,
+                             int fun, double* quad, double* Y, int ldy, int* depth = nullptr);
 
 // y-form sweep seeded by a device block (see kt_slq.cpp)
 void lanczos_sweep_y_block(kt_matrix_s* A, const DevCSR& M, int P, int m, const double* x, int ldx, int ncols,

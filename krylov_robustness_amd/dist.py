@@ -252,7 +252,7 @@ def reduce_callback(group=None, fail_on_rank=None):
 
 
 def mc_trace_sharded(Afun, n=None, tol=1e-3, maxit=10, isAreal=0, debug=0, seed=0, fun="exp",
-                     m=30, A=None, rank=None, world=None, allreduce=None, group=None, ctx=None,
+                     m=None, A=None, rank=None, world=None, allreduce=None, group=None, ctx=None,
                      force=False):
     """[tr, res, it] = mc_trace(...) on `world` GPUs: every
     rank recomputes S, Q and tr(Q' Afun Q) from the shared seed, the G-probe
@@ -263,7 +263,8 @@ def mc_trace_sharded(Afun, n=None, tol=1e-3, maxit=10, isAreal=0, debug=0, seed=
     `force`, which routes the round sums through the group's all-reduce)."""
     import ctypes as C
     from . import _lib
-    from .core import _dev
+    from .core import _afun_depth, _dev
+    m = _afun_depth(Afun if isinstance(Afun, str) else "matrix", m)
     if rank is None or world is None:
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized():
@@ -288,9 +289,10 @@ def mc_trace_sharded(Afun, n=None, tol=1e-3, maxit=10, isAreal=0, debug=0, seed=
     return float(tr.value), float(res.value), int(it.value)
 
 
-def trace_exp_sharded(A, method="lanczos", m=30, seed=0, rank=None, world=None, allreduce=None,
+def trace_exp_sharded(A, method="lanczos", m=None, seed=0, rank=None, world=None, allreduce=None,
                       group=None, ctx=None):
-    """trace_exp.m:1-7 (mc_trace(Afun, n, 1e-4, 1000, 1)) on `world` GPUs."""
+    """trace_exp.m:1-7 (mc_trace(Afun, n, 1e-4, 1000, 1)) on `world` GPUs;
+    method and m as core.trace_exp ("lanczos-auto": m is the depth cap)."""
     tr, _, _ = mc_trace_sharded(method, None, 1e-4, 1000, 1, 0, seed, "exp", m, A=A, rank=rank,
                                 world=world, allreduce=allreduce, group=group, ctx=ctx)
     return tr

@@ -319,18 +319,39 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     // tr = trace_exp(A)                                          trace_exp.m:1
     // trace_exp(A) as the reference's callers write it; an optional second
     // argument names the Afun: 'lanczos' (the north star's Lanczos-quadrature
-    // Afun, the default) or 'expmv' (the reference's own handle, trace_exp.m:5)
-    if (nrhs < 1 || nrhs > 2) mexErrMsgIdAndTxt("krylov_hip:nargin", "tr = trace_exp(A[, 'lanczos' | 'expmv'])");
-    int afun = KT_AFUN_LANCZOS;
-    if (nrhs == 2) {
+    // Afun at depth 30, the default), 'expmv' (the reference's own handle,
+    // trace_exp.m:5) or 'auto' (the Lanczos Afun with the depth chosen per
+    // column by its stopping test; a third argument caps the depth, default
+    // 128, at most 256).  A column that reaches the cap unconverged raises the
+    // warning TRACE_EXP:: Lanczos depth cap reached; the estimate is returned.
+    if (nrhs < 1 || nrhs > 3)
+        mexErrMsgIdAndTxt("krylov_hip:nargin", "tr = trace_exp(A[, 'lanczos' | 'expmv' | 'auto'[, m_max]])");
+    int afun = KT_AFUN_LANCZOS, m = 30;
+    if (nrhs >= 2) {
         char af[16] = {0};
         if (!mxIsChar(prhs[1]) || mxGetString(prhs[1], af, sizeof(af)) != 0 ||
-            (strcmp(af, "expmv") != 0 && strcmp(af, "lanczos") != 0))
-            mexErrMsgIdAndTxt("krylov_hip:afun", "trace_exp: the Afun must be 'lanczos' or 'expmv'");
+            (strcmp(af, "expmv") != 0 && strcmp(af, "lanczos") != 0 && strcmp(af, "auto") != 0))
+            mexErrMsgIdAndTxt("krylov_hip:afun", "trace_exp: the Afun must be 'lanczos' or 'expmv' (or 'auto')");
         if (strcmp(af, "expmv") == 0) afun = KT_AFUN_EXPMV;
+        if (strcmp(af, "auto") == 0) {
+            afun = KT_AFUN_LANCZOS_AUTO;
+            m = 0;
+        }
+    }
+    if (nrhs == 3) {
+        if (afun != KT_AFUN_LANCZOS_AUTO || !mxIsDouble(prhs[2]) || mxGetNumberOfElements(prhs[2]) != 1)
+            mexErrMsgIdAndTxt("krylov_hip:afun", "trace_exp: a depth cap (a scalar) goes with 'auto' only");
+        m = (int)mxGetScalar(prhs[2]);
     }
     double tr = 0.0;
-    check(kt_trace_exp(matrix_arg(prhs[0]), afun, 30, 0, &tr), "trace_exp");
+    kt_matrix_t Ad = matrix_arg(prhs[0]);
+    int64_t capped0 = 0, capped1 = 0;
+    if (afun == KT_AFUN_LANCZOS_AUTO) check(kt_context_stat(context(), 6, &capped0), "trace_exp");
+    check(kt_trace_exp(Ad, afun, m, 0, &tr), "trace_exp");
+    if (afun == KT_AFUN_LANCZOS_AUTO) {
+        check(kt_context_stat(context(), 6, &capped1), "trace_exp");
+        if (capped1 > capped0) mexWarnMsgIdAndTxt("TRACE_EXP:depthcap", "TRACE_EXP:: Lanczos depth cap reached");
+    }
     plhs[0] = scalar(tr);
 #elif defined(KT_ENTRY_MC_TRACE)
     // [tr, res, it] = mc_trace(Afun, n, tol, maxit, isAreal, debug)   mc_trace.m:1

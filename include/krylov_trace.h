@@ -350,7 +350,9 @@ int kt_eigs_leading(kt_matrix_t A, double tol, int maxit, double* lambda, double
  * launch of the named kernel while enabled).  kernel: 0 = the probe-Lanczos
  * gather pass (k_spmm_lanczos in the y-form sweep, k_spmm_dot = K1 in the
  * explicit sweep), 1 = K2 (k_update, explicit sweep only), 2 = the y-form
- * start pass (k_spmm_lanczos_start), 3 = the y-form pass of a sweep seeded
+ * start pass (k_spmm_lanczos_start), 5 = the first step of a compact y-form
+ * sweep alone (k_spmm_lanczos_first; the launch is also counted among the
+ * sweep's passes in 0), 3 = the y-form pass of a sweep seeded
  * by a given block (k_spmm_lanczos in mc_trace's quadrature-only columns),
  * 4 = the expmv Taylor-term kernel (k_expmv_rows / k_expmv_step, one launch
  * per term; a term queued past its stage's stop is a short no-op launch).
@@ -385,7 +387,9 @@ int kt_debug_delay(kt_context_t ctx, int lane, double microseconds);
  * creation.  stat 5: the largest Lanczos depth the adaptive Afun
  * (KT_AFUN_LANCZOS_AUTO, kt_lanczos_fmv_auto) used for a column, stat 6: its
  * columns that reached the depth cap unconverged, both since context
- * creation. */
+ * creation.  stat 7: kt_slq_trace y-form sweeps that carried y_0 as int16 row
+ * sums (kt_host_int0_applies; KT_SLQ_INT0=0, read per call, turns the form
+ * off), since context creation. */
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value);
 
 /* Threads of the process-wide host pool (the per-column / per-candidate
@@ -395,6 +399,13 @@ int kt_context_stat(kt_context_t ctx, int stat, int64_t* value);
  * divided by LOCAL_WORLD_SIZE, the ranks torchrun started on this node),
  * at least 1; KT_HOST_THREADS overrides.  Fixed at the pool's first use. */
 int kt_host_threads(void);
+
+/* Whether kt_slq_trace's y-form sweeps of depth m keep y_0 = A z / ||z|| as
+ * int16 row sums on a matrix whose longest row has max_row entries: the
+ * matrix is unit-weight (each sum is then an integer of magnitude <= the
+ * row's length), max_row <= 32767 and m >= 3.  The results do not depend on
+ * it, bit for bit.  Host only. */
+int kt_host_int0_applies(int unit_weight, int64_t max_row, int m, int* applies);
 
 #ifdef __cplusplus
 }

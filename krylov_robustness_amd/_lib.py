@@ -112,6 +112,7 @@ SIGNATURES = [
     ("kt_profile_read_width", C.c_int, [_ctx_p, C.c_int, C.c_int, _i64p, _dp]),
     ("kt_context_stat", C.c_int, [_ctx_p, C.c_int, _i64p]),
     ("kt_host_threads", C.c_int, []),
+    ("kt_host_int0_applies", C.c_int, [C.c_int, C.c_int64, C.c_int, _ip]),
 ]
 
 _lib = None

@@ -84,7 +84,8 @@ class Context:
         """kt_context_stat: 0 y-form sweeps redone, 1 fun_update dense
         fallbacks, 2 basis columns of the last fun_update, 3 expmv calls,
         4 Taylor terms those calls executed, 5 the largest depth the adaptive
-        Lanczos Afun used, 6 its columns that reached the depth cap."""
+        Lanczos Afun used, 6 its columns that reached the depth cap, 7 y-form
+        sweeps that carried y_0 as int16 row sums."""
         v = C.c_int64()
         _lib.check(_lib.load().kt_context_stat(self._h, int(which), C.byref(v)))
         return int(v.value)

@@ -133,7 +133,12 @@ struct ProfSlot {
     std::vector<std::pair<int, std::pair<int64_t, double>>> by_tag;
 };
 
-enum { PROF_SPMM = 0, PROF_UPDATE = 1, PROF_START = 2, PROF_YBLOCK = 3, PROF_EXPMV = 4, PROF_NSLOTS = 5 };
+// PROF_FIRST: the compact sweep's first step (k_spmm_lanczos_first) alone; the
+// launch is also one of the sweep's step passes in PROF_SPMM
+enum {
+    PROF_SPMM = 0, PROF_UPDATE = 1, PROF_START = 2, PROF_YBLOCK = 3, PROF_EXPMV = 4, PROF_FIRST = 5,
+    PROF_NSLOTS = 6
+};
 
 // Buffers of one probe-sweep lane (kt_slq.cpp); two lanes let two sweeps
 // run on two streams.
@@ -241,6 +246,7 @@ struct kt_context_s {
     int64_t expmv_terms = 0;   // Taylor terms those calls executed (one A b product each, expmv.m:75)
     int64_t adapt_max_depth = 0;  // adaptive Lanczos Afun: the largest depth a column used
     int64_t adapt_capped = 0;     // ... and its columns that reached the depth cap unconverged
+    int64_t int0_sweeps = 0;      // y-form sweeps that carried y_0 as int16 row sums (kt_slq.h int0_applies)
     int ky_flags = 8;   // y-form pass flags (8 = nontemporal store of y_{j+1}, +0.3 %)
     bool yform = true;  // KT_SLQ_YFORM=0: the hot path runs the explicit K1/K2 sweep
     void* blas = nullptr;  // rocblas_handle, created on first block-Krylov use
@@ -272,6 +278,7 @@ struct DevCSR {
     int* lower = nullptr;
     int* long_rows = nullptr;  // rows with degree > long_thresh, heaviest first
     int n_long = 0;
+    int max_row = 0;           // the longest row's length
     int n_heavy = 0;           // the first n_heavy long rows have degree > kExpmvCoopThresh
     int* med_rows = nullptr;   // rows with kMedThresh < degree <= long_thresh (expmv terms)
     int n_med = 0;

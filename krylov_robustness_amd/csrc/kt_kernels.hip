@@ -91,7 +91,11 @@ template <int P> using GeoB = GeoW<P, (P >= 16) ? kBlkVW : (P >= 2) ? 2 : 1>;
 // own b is never read and (A - mu I) b is A b.
 // FLAGS bit 6 (y-form passes): also form the Lanczos vector v_{j+1} (the
 // basis of f(A) x = ||x|| V f(T) e1) from the pass's own rows.
-enum : int { KF_NT = 1, KF_UNIT = 2, KF_MLP = 4, KF_NTY = 8, KF_SC1 = 16, KF_MU0 = 32, KF_VB = 64 };
+// FLAGS bit 7 (k_spmm_lanczos, a compact sweep's second step): Yold = y_0 is
+// the start pass's n x P int16 table, read as s0 * (double)k (ld_i16).
+enum : int {
+    KF_NT = 1, KF_UNIT = 2, KF_MLP = 4, KF_NTY = 8, KF_SC1 = 16, KF_MU0 = 32, KF_VB = 64, KF_I16 = 128
+};
 
 typedef unsigned int kt_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int kt_u32x2 __attribute__((ext_vector_type(2)));
@@ -201,6 +205,36 @@ template <int FLAGS, class T> __device__ __forceinline__ T ld_stream(const T* p)
 template <int FLAGS, int VEC>
 __device__ __forceinline__ typename VecT<VEC>::T ld_gather(const double* p) {
     return VecT<VEC>::load(p);
+}
+
+// y_0 of a compact y-form sweep: on a unit-weight matrix the
+// start pass's row sums are integers k, |k| <= the row's degree, kept as an
+// n x P int16 table, and y_0[r, p] = s0 * (double)k is the very product the
+// fp64 start pass stores.  A lane's VEC (<= 2) probes are one load.  The
+// product is rounded on its own (no contraction into the consumer's add), so
+// every later sum sees the stored fp64 value's bits.
+template <int VEC, bool NT = false>
+__device__ __forceinline__ typename VecT<VEC>::T ld_i16(const int16_t* p, double s0) {
+#pragma clang fp contract(off)
+    static_assert(VEC == 1 || VEC == 2, "one 2- or 4-byte load per lane");
+    if constexpr (VEC == 1) {
+        const int16_t k = NT ? __builtin_nontemporal_load(p) : *p;
+        return s0 * (double)k;
+    } else {
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+        const uint32_t w = NT ? __builtin_nontemporal_load(q) : *q;
+        const double lo = s0 * (double)(int16_t)(w & 0xffffu);
+        const double hi = s0 * (double)(int16_t)(w >> 16);
+        return double2(lo, hi);
+    }
+}
+template <int VEC> __device__ __forceinline__ void st_i16(int16_t* p, const double* k) {
+    if constexpr (VEC == 1) {
+        *p = (int16_t)(int)k[0];
+    } else {
+        const uint32_t lo = (uint16_t)(int16_t)(int)k[0], hi = (uint16_t)(int16_t)(int)k[1];
+        *reinterpret_cast<uint32_t*>(p) = lo | (hi << 16);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -556,13 +590,18 @@ __device__ __forceinline__ void row_epilogue_y(int row, int p0, const double* s,
                                                double* d2, __amdgpu_buffer_rsrc_t orsrc,
                                                const double* __restrict__ Vc = nullptr,
                                                const double* __restrict__ Vo = nullptr,
-                                               double* __restrict__ Vn = nullptr, int bcols = 0) {
+                                               double* __restrict__ Vn = nullptr, int bcols = 0,
+                                               double s0 = 0.0) {
     using V = VecT<G::VEC>;
     const int64_t off = (int64_t)row * P + p0;
     const typename V::T xi = V::load(X + off);
     row_basis_y<P, FLAGS, G>(off, p0, xi, cg, ca, cb, Vc, Vo, Vn, bcols);
     typename V::T yo;
-    if (has_old) yo = V::load_nt(Yold + off);
+    if constexpr (FLAGS & KF_I16) {  // Yold is the compact y_0 table (has_old holds)
+        yo = ld_i16<G::VEC, true>(reinterpret_cast<const int16_t*>(Yold) + off, s0);
+    } else {
+        if (has_old) yo = V::load_nt(Yold + off);
+    }
     typename V::T o;
     double* op = reinterpret_cast<double*>(&o);
 #pragma unroll
@@ -660,7 +699,10 @@ __global__ __launch_bounds__(BLOCK) void k_spmm_lanczos_start(
             d1[e] = fma(x, u, d1[e]);
             d2[e] = fma(u, u, d2[e]);
         }
-        if constexpr (FLAGS & KF_SC1) store_sc1<G::VEC>(orsrc, (uint32_t)(((int64_t)row * P + p0) * 8), op);
+        // KF_I16 (unit weights, every row <= 32,767 long): Out is the n x P
+        // int16 table of the integer sums; the fp64 y_0 = s0 * sum is not stored
+        if constexpr (FLAGS & KF_I16) st_i16<G::VEC>(reinterpret_cast<int16_t*>(Out) + (int64_t)row * P + p0, sum);
+        else if constexpr (FLAGS & KF_SC1) store_sc1<G::VEC>(orsrc, (uint32_t)(((int64_t)row * P + p0) * 8), op);
         else if constexpr (FLAGS & KF_NTY) V::store_nt(Out + (int64_t)row * P + p0, o);
         else V::store(Out + (int64_t)row * P + p0, o);
     };
@@ -724,7 +766,8 @@ __global__ __launch_bounds__(BLOCK) void k_spmm_lanczos(
     int n, const double* __restrict__ X, const double* __restrict__ Yold, double* __restrict__ Out,
     const double* __restrict__ coef, double* __restrict__ partial,
     const int* __restrict__ long_rows, int n_long, int long_thresh, int long_blocks,
-    const double* __restrict__ Vc, const double* __restrict__ Vo, double* __restrict__ Vn, int bcols) {
+    const double* __restrict__ Vc, const double* __restrict__ Vo, double* __restrict__ Vn, int bcols,
+    double s0) {
     using G = GeoKY<P>;
     constexpr int WAVES = BLOCK / 64;
     const int lane = threadIdx.x & 63;
@@ -763,7 +806,7 @@ __global__ __launch_bounds__(BLOCK) void k_spmm_lanczos(
                 for (int e = 0; e < G::VEC; ++e) s[e] += kt::shfl_xor(s[e], o);
             if (grp == 0)
                 row_epilogue_y<P, FLAGS, G>(row, p0, s, cg, ca, cb, has_old, X, Yold, Out, d0, d1, d2,
-                                            orsrc, Vc, Vo, Vn, bcols);
+                                            orsrc, Vc, Vo, Vn, bcols, s0);
         }
     } else {
         const int sb = blockIdx.x - long_blocks;
@@ -777,7 +820,147 @@ __global__ __launch_bounds__(BLOCK) void k_spmm_lanczos(
             for (int e = 0; e < G::VEC; ++e) s[e] = 0.0;
             gather_row<P, FLAGS, G>(beg, end, 1, p0, col, val, X, s);
             row_epilogue_y<P, FLAGS, G>(row, p0, s, cg, ca, cb, has_old, X, Yold, Out, d0, d1, d2,
-                                        orsrc, Vc, Vo, Vn, bcols);
+                                        orsrc, Vc, Vo, Vn, bcols, s0);
+        }
+    }
+
+#pragma unroll
+    for (int o = G::LPR; o < 64; o <<= 1)
+#pragma unroll
+        for (int e = 0; e < G::VEC; ++e) {
+            d0[e] += kt::shfl_xor(d0[e], o);
+            d1[e] += kt::shfl_xor(d1[e], o);
+            d2[e] += kt::shfl_xor(d2[e], o);
+        }
+    __shared__ double red[WAVES][3][P];
+    if (grp == 0) {
+#pragma unroll
+        for (int e = 0; e < G::VEC; ++e) {
+            red[wave][0][p0 + e] = d0[e];
+            red[wave][1][p0 + e] = d1[e];
+            red[wave][2][p0 + e] = d2[e];
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < 3 * P; t += BLOCK) {  // slot t = q * P + p
+        const int q = t / P, p = t % P;
+        double v = 0.0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) v += red[w][q][p];
+        partial[(int64_t)t * gridDim.x + blockIdx.x] = v;
+    }
+}
+
+// row_gather's sum (unit weights, the same 4-deep shape and nonzero order, so
+// partial sums round identically) with the gathered rows read from the
+// compact y_0 table: 2P bytes per row instead of 8P.
+template <int P, int FLAGS, class G>
+__device__ __forceinline__ void row_gather_i16(int k0, int end, int stride, int p0,
+                                               const int* __restrict__ col,
+                                               const int16_t* __restrict__ T, double s0, double* s) {
+    using V = VecT<G::VEC>;
+    int k = k0;
+    for (; k + 3 * stride < end; k += 4 * stride) {
+        const int c0 = ld_stream<FLAGS>(col + k), c1 = ld_stream<FLAGS>(col + k + stride);
+        const int c2 = ld_stream<FLAGS>(col + k + 2 * stride);
+        const int c3 = ld_stream<FLAGS>(col + k + 3 * stride);
+        const typename V::T x0 = ld_i16<G::VEC>(T + (int64_t)c0 * P + p0, s0);
+        const typename V::T x1 = ld_i16<G::VEC>(T + (int64_t)c1 * P + p0, s0);
+        const typename V::T x2 = ld_i16<G::VEC>(T + (int64_t)c2 * P + p0, s0);
+        const typename V::T x3 = ld_i16<G::VEC>(T + (int64_t)c3 * P + p0, s0);
+#pragma unroll
+        for (int e = 0; e < G::VEC; ++e) {
+            s[e] = fma(1.0, V::get(x0, e), s[e]);
+            s[e] = fma(1.0, V::get(x1, e), s[e]);
+            s[e] = fma(1.0, V::get(x2, e), s[e]);
+            s[e] = fma(1.0, V::get(x3, e), s[e]);
+        }
+    }
+    for (; k < end; k += stride) {
+        const int c0 = ld_stream<FLAGS>(col + k);
+        const typename V::T x0 = ld_i16<G::VEC>(T + (int64_t)c0 * P + p0, s0);
+#pragma unroll
+        for (int e = 0; e < G::VEC; ++e) s[e] = fma(1.0, V::get(x0, e), s[e]);
+    }
+}
+
+// First ordinary step of a compact sweep (unit weights): k_spmm_lanczos with
+// X = y_0 gathered and read back as own rows from the int16 table T
+// (y_0 = s0 * (double)T), no Yold; y_1 and the partials as k_spmm_lanczos
+// stores them, bit for bit.  Same row groups, long-row waves, grid, row order
+// and fixed-order reduction.
+template <int P, int BLOCK, int FLAGS>
+__global__ __launch_bounds__(BLOCK) void k_spmm_lanczos_first(
+    const int* __restrict__ row_ptr, const int* __restrict__ col, int n, const int16_t* __restrict__ T,
+    double s0, double* __restrict__ Out, const double* __restrict__ coef, double* __restrict__ partial,
+    const int* __restrict__ long_rows, int n_long, int long_thresh, int long_blocks) {
+    using G = GeoKY<P>;
+    using V = VecT<G::VEC>;
+    constexpr int WAVES = BLOCK / 64;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int sub = lane % G::LPR;
+    const int grp = lane / G::LPR;
+    const int p0 = sub * G::VEC;
+    __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
+        Out, 0, (FLAGS & KF_SC1) ? (int)((int64_t)n * P * 8) : 0, 0x00020000);
+
+    double d0[G::VEC], d1[G::VEC], d2[G::VEC];
+#pragma unroll
+    for (int e = 0; e < G::VEC; ++e) d0[e] = d1[e] = d2[e] = 0.0;
+    double cg[G::VEC], ca[G::VEC];
+#pragma unroll
+    for (int e = 0; e < G::VEC; ++e) {
+        cg[e] = coef[p0 + e];
+        ca[e] = coef[P + p0 + e];
+    }
+    // row_epilogue_y with has_old = false and the own row from T
+    auto epilogue = [&](int row, const double* s) {
+        const int64_t off = (int64_t)row * P + p0;
+        const typename V::T xi = ld_i16<G::VEC>(T + off, s0);
+        typename V::T o;
+        double* op = reinterpret_cast<double*>(&o);
+#pragma unroll
+        for (int e = 0; e < G::VEC; ++e) {
+            const double x = V::get(xi, e);
+            const double u = fma(-ca[e], x, cg[e] * s[e]);
+            op[e] = u;
+            d0[e] = fma(x, s[e], d0[e]);
+            d1[e] = fma(x, u, d1[e]);
+            d2[e] = fma(u, u, d2[e]);
+        }
+        if constexpr (FLAGS & KF_SC1) store_sc1<G::VEC>(orsrc, (uint32_t)(off * 8), op);
+        else if constexpr (FLAGS & KF_NTY) V::store_nt(Out + off, o);
+        else V::store(Out + off, o);
+    };
+
+    if ((int)blockIdx.x < long_blocks) {
+        for (int li = blockIdx.x * WAVES + wave; li < n_long; li += long_blocks * WAVES) {
+            const int row = long_rows[li];
+            const int beg = row_ptr[row];
+            const int end = row_ptr[row + 1];
+            double s[G::VEC];
+#pragma unroll
+            for (int e = 0; e < G::VEC; ++e) s[e] = 0.0;
+            row_gather_i16<P, FLAGS, G>(beg + grp, end, G::GPW, p0, col, T, s0, s);
+#pragma unroll
+            for (int o = G::LPR; o < 64; o <<= 1)
+#pragma unroll
+                for (int e = 0; e < G::VEC; ++e) s[e] += kt::shfl_xor(s[e], o);
+            if (grp == 0) epilogue(row, s);
+        }
+    } else {
+        const int sb = blockIdx.x - long_blocks;
+        const int groups_total = (gridDim.x - long_blocks) * WAVES * G::GPW;
+        for (int row = (sb * WAVES + wave) * G::GPW + grp; row < n; row += groups_total) {
+            const int beg = ld_stream<FLAGS>(row_ptr + row);
+            const int end = ld_stream<FLAGS>(row_ptr + row + 1);
+            if (end - beg > long_thresh) continue;  // owned by a long-row wave
+            double s[G::VEC];
+#pragma unroll
+            for (int e = 0; e < G::VEC; ++e) s[e] = 0.0;
+            row_gather_i16<P, FLAGS, G>(beg, end, 1, p0, col, T, s0, s);
+            epilogue(row, s);
         }
     }
 
@@ -2367,13 +2550,20 @@ hipError_t launch_spmm_lanczos(int P, int flags, int grid, const int* rp, const 
                                const double* va, int n, const double* X, const double* Yold,
                                double* Out, const double* coef, double* partial,
                                const int* long_rows, int n_long, int long_thresh, int long_blocks,
-                               hipStream_t st, const double* Vc, const double* Vo, double* Vn, int bcols) {
+                               hipStream_t st, const double* Vc, const double* Vo, double* Vn, int bcols,
+                               double s0) {
     return dispatch_p(P, [&](auto c) {
         constexpr int PP = decltype(c)::value;
 #define KT_KY(F)                                                                                   \
     k_spmm_lanczos<PP, kBlock, F><<<grid, kBlock, 0, st>>>(rp, ci, va, n, X, Yold, Out, coef, partial, \
                                                            long_rows, n_long, long_thresh, long_blocks, \
-                                                           Vc, Vo, Vn, bcols)
+                                                           Vc, Vo, Vn, bcols, s0)
+        if (flags & KF_I16) {  // a compact sweep's second step (unit weights, no basis): Yold = int16 y_0
+            if (flags & KF_SC1) KT_KY(KF_UNIT | KF_I16 | KF_SC1);
+            else if (flags & KF_NTY) KT_KY(KF_UNIT | KF_I16 | KF_NTY);
+            else KT_KY(KF_UNIT | KF_I16);
+            return;
+        }
         if (Vn) {  // the basis-forming pass (KF_VB)
             if (flags & KF_UNIT) {
                 if (flags & KF_SC1) KT_KY(KF_UNIT | KF_SC1 | KF_VB);
@@ -2440,6 +2630,10 @@ hipError_t launch_spmm_lanczos_start(int P, int flags, int grid, const int* rp, 
     k_spmm_lanczos_start<PP, kBlock, F><<<grid, kBlock, 0, st>>>(rp, ci, va, n, S, s0, Out, partial, \
                                                                  long_rows, n_long, long_thresh,  \
                                                                  long_blocks)
+        if (flags & KF_I16) {  // compact start: Out is the n x P int16 table (unit weights)
+            KT_KS(KF_UNIT | KF_I16);
+            return;
+        }
         switch (flags & (KF_UNIT | KF_NTY | KF_SC1)) {
         case 0: KT_KS(0); break;
         case KF_UNIT: KT_KS(KF_UNIT); break;
@@ -2450,6 +2644,23 @@ hipError_t launch_spmm_lanczos_start(int P, int flags, int grid, const int* rp, 
         default: KT_KS(KF_UNIT | KF_SC1); break;
         }
 #undef KT_KS
+    });
+}
+
+hipError_t launch_spmm_lanczos_first(int P, int flags, int grid, const int* rp, const int* ci, int n,
+                                     const int16_t* T, double s0, double* Out, const double* coef,
+                                     double* partial, const int* long_rows, int n_long, int long_thresh,
+                                     int long_blocks, hipStream_t st) {
+    return dispatch_p(P, [&](auto c) {
+        constexpr int PP = decltype(c)::value;
+#define KT_KF(F)                                                                                  \
+    k_spmm_lanczos_first<PP, kBlock, F><<<grid, kBlock, 0, st>>>(rp, ci, n, T, s0, Out, coef, partial, \
+                                                                 long_rows, n_long, long_thresh,   \
+                                                                 long_blocks)
+        if (flags & KF_SC1) KT_KF(KF_UNIT | KF_SC1);
+        else if (flags & KF_NTY) KT_KF(KF_UNIT | KF_NTY);
+        else KT_KF(KF_UNIT);
+#undef KT_KF
     });
 }
 

@@ -88,13 +88,21 @@ hipError_t launch_norm(int P, const double* partial, int nblk, double* k2s, doub
 // for launch_ycoef, the per-probe coefficient step).
 // Vn != nullptr: also v_{j+1} = g y_j - a v_j - b v_{j-1} into basis slot Vn
 // from slots Vc (v_j) and Vo (v_{j-1}, nullptr at j = 0), columns < bcols
-// (every slot n x P, row-major)
+// (every slot n x P, row-major).  flags bit 7 (a compact sweep's second
+// step; unit weights, no basis): Yold is the start pass's n x P int16 table,
+// y_0 = s0 * (double)Yold
 hipError_t launch_spmm_lanczos(int P, int flags, int grid, const int* rp, const int* ci,
                                const double* va, int n, const double* X, const double* Yold,
                                double* Out, const double* coef, double* partial,
                                const int* long_rows, int n_long, int long_thresh, int long_blocks,
                                hipStream_t st, const double* Vc = nullptr, const double* Vo = nullptr,
-                               double* Vn = nullptr, int bcols = 0);
+                               double* Vn = nullptr, int bcols = 0, double s0 = 0.0);
+// First ordinary step of a compact sweep (unit weights): launch_spmm_lanczos
+// with X = y_0 = s0 * (double)T read from the int16 table T and no Yold
+hipError_t launch_spmm_lanczos_first(int P, int flags, int grid, const int* rp, const int* ci, int n,
+                                     const int16_t* T, double s0, double* Out, const double* coef,
+                                     double* partial, const int* long_rows, int n_long, int long_thresh,
+                                     int long_blocks, hipStream_t st);
 // The last pass of a y-form sweep: only slab 0, X'A X per probe, from each
 // row's strictly-lower prefix and diagonal (lower = DevCSR::lower; slabs 1, 2
 // are written as zeros).  Vn as above.
@@ -106,6 +114,8 @@ hipError_t launch_spmm_quadform(int P, int flags, int grid, const int* rp, const
                                 double* Vn = nullptr, int bcols = 0);
 hipError_t launch_rademacher_signs(int P, int n, uint64_t seed, int64_t probe_base,
                                   const int* perm, uint32_t* S, hipStream_t st);
+// flags bit 7 (unit weights): Out is the n x P int16 table of the row sums
+// (y_0 = s0 * sum is not stored); the partials are the same
 hipError_t launch_spmm_lanczos_start(int P, int flags, int grid, const int* rp, const int* ci,
                                      const double* va, int n, const uint32_t* S, double s0,
                                      double* Out, double* partial, const int* long_rows, int n_long,

@@ -11,6 +11,7 @@
 
 #include "kt_internal.h"
 #include "kt_launch.h"
+#include "kt_slq.h"
 #include "kt_order.h"
 #include "kt_pool.h"
 
@@ -132,7 +133,7 @@ void DevCSR::release() {
     rowptr = col = lower = long_rows = perm = med_rows = short_tasks = med_tasks = nullptr;
     ck_beg = ck_end = sp_rows = sp_first = nullptr;
     val = nullptr;
-    n_long = n_heavy = n_med = n_short = n_chunks = n_split = 0;
+    n_long = max_row = n_heavy = n_med = n_short = n_chunks = n_split = 0;
     built = false;
 }
 
@@ -185,8 +186,11 @@ void build_csr(kt_matrix_s* A, const std::vector<int32_t>& new2old, DevCSR& out,
         }
     }
     std::vector<int32_t> lr;
-    for (int64_t r = 0; r < n; ++r)
+    int32_t max_row = 0;
+    for (int64_t r = 0; r < n; ++r) {
+        max_row = std::max(max_row, rp32[r + 1] - rp32[r]);
         if (rp32[r + 1] - rp32[r] > A->long_thresh) lr.push_back((int32_t)r);
+    }
     std::stable_sort(lr.begin(), lr.end(), [&](int32_t a, int32_t b) {
         return rp32[a + 1] - rp32[a] > rp32[b + 1] - rp32[b];
     });
@@ -318,6 +322,7 @@ void build_csr(kt_matrix_s* A, const std::vector<int32_t>& new2old, DevCSR& out,
         // staging buffer is not rewritten before the next build's sync above)
         if (sync) KT_HIP(hipStreamSynchronize(A->ctx->stream));
         out.n_long = (int)lr.size();
+        out.max_row = max_row;
         out.n_heavy = 0;
         while (out.n_heavy < out.n_long &&
                rp32[lr[out.n_heavy] + 1] - rp32[lr[out.n_heavy]] > kExpmvCoopThresh) ++out.n_heavy;
@@ -600,14 +605,21 @@ int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* tot
 
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value) {
     KT_GUARD_BEGIN
-    if (!ctx || !value || stat < 0 || stat > 6) fail(KT_ERR_ARG, "bad stat query");
-    const int64_t v[7] = {ctx->yform_redone, ctx->fu_dense, ctx->fu_last_cols, ctx->expmv_calls,
-                          ctx->expmv_terms, ctx->adapt_max_depth, ctx->adapt_capped};
+    if (!ctx || !value || stat < 0 || stat > 7) fail(KT_ERR_ARG, "bad stat query");
+    const int64_t v[8] = {ctx->yform_redone, ctx->fu_dense, ctx->fu_last_cols, ctx->expmv_calls,
+                          ctx->expmv_terms, ctx->adapt_max_depth, ctx->adapt_capped, ctx->int0_sweeps};
     *value = v[stat];
     KT_GUARD_END
 }
 
 int kt_host_threads(void) { return kt::HostPool::get().threads(); }
+
+int kt_host_int0_applies(int unit_weight, int64_t max_row, int m, int* applies) {
+    KT_GUARD_BEGIN
+    if (!applies) fail(KT_ERR_ARG, "applies is NULL");
+    *applies = kt::int0_applies(unit_weight != 0, max_row, m) ? 1 : 0;
+    KT_GUARD_END
+}
 
 int kt_profile_reset(kt_context_t ctx) {
     KT_GUARD_BEGIN

@@ -185,8 +185,9 @@ void lanczos_sweep(kt_matrix_s* A, const DevCSR& M, int P, int m, uint64_t seed,
 // step by step (start(), step(j) for j < m - 1, finish()), so sweeps on
 // different lanes are queued launch by launch.
 YSweep::YSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, uint64_t seed_, int64_t probe_base_,
-               double* rec_host_, int lane_)
-    : A(A_), M(M_), P(P_), m(m_), seed(seed_), probe_base(probe_base_), rec_host(rec_host_), lane(lane_) {
+               double* rec_host_, int lane_, bool int0_)
+    : A(A_), M(M_), P(P_), m(m_), seed(seed_), probe_base(probe_base_), rec_host(rec_host_), lane(lane_),
+      int0(int0_) {
     kt_context_s* ctx = A->ctx;
     n = (int)A->n;
     if (lane < 0 || lane > 3) fail(KT_ERR_ARG, "sweep lane out of range");
@@ -199,8 +200,13 @@ YSweep::YSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, uint64_t seed_
     grid1 = grid + lblocks;
     SweepBufs& w = ctx->ws.sweep[lane];
     blk_bytes = sizeof(double) * (size_t)n * P;
+    // X1: the packed sign table and, in the compact form, y_0's int16 table
+    // behind it (not in y_0's own slot Y: the second step stores y_2 there
+    // while other rows still read y_0, and the two layouts' rows do not
+    // coincide).  2nP bytes after <= 4n ceil(P/32): inside the block but for tiny n.
+    const size_t t0_off = (sizeof(uint32_t) * (size_t)n * ((P + 31) / 32) + 127) & ~(size_t)127;
     w.X0.ensure(blk_bytes);
-    w.X1.ensure(blk_bytes);
+    w.X1.ensure(int0 ? std::max(blk_bytes, t0_off + sizeof(int16_t) * (size_t)n * P) : blk_bytes);
     w.Y.ensure(blk_bytes);
     w.partial.ensure(sizeof(double) * (size_t)3 * P * grid1);  // slot-major [3P][grid1]
     w.coef.ensure(sizeof(double) * 9 * P);
@@ -212,20 +218,23 @@ YSweep::YSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, uint64_t seed_
     flags = ctx->ky_flags | (A->unit_values ? 2 : 0);
     if (blk_bytes >= ((size_t)1 << 31)) flags &= ~16;  // sc1 buffer stores take 32-bit offsets
     Z = w.X1.as<uint32_t>();
-    Xc = w.Y.as<double>();   // y_j
+    if (int0) T0 = reinterpret_cast<int16_t*>(w.X1.as<char>() + t0_off);
+    Xc = w.Y.as<double>();   // y_j (compact form: y_0 is T0, this slot is first used for y_2)
     Yo = nullptr;            // y_{j-1} (none at j = 0)
     Ot = w.X0.as<double>();  // y_{j+1}
+    s0 = 1.0 / std::sqrt((double)n);  // v_0 = z / ||z||, ||z||^2 = n
 }
 
 void YSweep::start() {
     kt_context_s* ctx = A->ctx;
-    const double s0 = 1.0 / std::sqrt((double)n);  // v_0 = z / ||z||, ||z||^2 = n
     // probes as a packed sign table (n x ceil(P/32) words), gathered by the
     // start pass instead of an 8nP-byte fp64 block
     KT_HIP(launch_rademacher_signs(P, n, seed, probe_base, M.perm, Z, st));
     prof_begin(ctx, PROF_START, st, P);
-    KT_HIP(launch_spmm_lanczos_start(P, flags, grid1, M.rowptr, M.col, M.val, n, Z, s0, Xc, part, M.long_rows,
-                                     M.n_long, A->long_thresh, lblocks, st));
+    if (int0) ctx->int0_sweeps += 1;
+    KT_HIP(launch_spmm_lanczos_start(P, flags | (int0 ? 128 : 0), grid1, M.rowptr, M.col, M.val, n, Z, s0,
+                                     int0 ? reinterpret_cast<double*>(T0) : Xc, part, M.long_rows, M.n_long,
+                                     A->long_thresh, lblocks, st));
     prof_end(ctx, PROF_START, st);
     KT_HIP(launch_ycoef(P, part, grid1, 1, m == 1, s0, ys, rec_at(0, 0), rec_at(1, 0), rec_at(2, 0), guard, st));
 }
@@ -234,9 +243,18 @@ void YSweep::step(int j) {
     kt_context_s* ctx = A->ctx;
     prof_begin(ctx, PROF_SPMM, st, P);
     const bool last = j + 2 == m;  // y_{m} is never used: alpha_{m-1} needs only X'A X
-    if (last)
+    if (int0 && j == 0) {  // m >= 3: never the last pass; also timed alone in its own slot
+        prof_begin(ctx, PROF_FIRST, st, P);
+        KT_HIP(launch_spmm_lanczos_first(P, flags, grid1, M.rowptr, M.col, n, T0, s0, Ot, ys + 6 * P, part,
+                                         M.long_rows, M.n_long, A->long_thresh, lblocks, st));
+        prof_end(ctx, PROF_FIRST, st);
+    } else if (last)
         KT_HIP(launch_spmm_quadform(P, flags, grid1, M.rowptr, M.col, M.val, M.lower, n, Xc, ys + 6 * P, part,
                                     M.long_rows, M.n_long, A->long_thresh, lblocks, st));
+    else if (int0 && j == 1)  // Yold = y_0 from the int16 table
+        KT_HIP(launch_spmm_lanczos(P, flags | 128, grid1, M.rowptr, M.col, M.val, n, Xc,
+                                   reinterpret_cast<const double*>(T0), Ot, ys + 6 * P, part, M.long_rows,
+                                   M.n_long, A->long_thresh, lblocks, st, nullptr, nullptr, nullptr, 0, s0));
     else
         KT_HIP(launch_spmm_lanczos(P, flags, grid1, M.rowptr, M.col, M.val, n, Xc, Yo, Ot, ys + 6 * P, part,
                                    M.long_rows, M.n_long, A->long_thresh, lblocks, st));
@@ -904,12 +922,16 @@ static int slq_submit(kt_matrix_s* A, int fun, int m, uint64_t seed, int64_t pro
     const char* le = getenv("KT_SLQ_LANES");
     const int lanes_env = le ? std::max(1, std::min(4, atoi(le))) : (ctx->yform ? 2 : 3);
     pd.lanes = (int)std::max<int64_t>(1, std::min<int64_t>(pd.nsweeps, lanes_env));
+    // KT_SLQ_INT0=0: the y-form sweeps keep y_0 in fp64 (the A/B of the compact form)
+    const char* ie = getenv("KT_SLQ_INT0");
+    const bool int0_env = !(ie && ie[0] == '0');
     if (pd.nsweeps) {
         KT_HIP(hipSetDevice(ctx->device));
         PinnedBuf& hb = w.host_trec[ticket & 1];
         hb.ensure(sizeof(double) * pd.rec * pd.nsweeps);
         double* htrec = hb.as<double>();
         const DevCSR& H = hub_csr(A);
+        const bool int0 = int0_env && int0_applies(A->unit_values, H.max_row, m);
         // profiling: the previous calls' events are folded in while this
         // call's sweeps run on the device
         prof_recycle(ctx);
@@ -923,7 +945,7 @@ static int slq_submit(kt_matrix_s* A, int fun, int m, uint64_t seed, int64_t pro
                 std::vector<std::unique_ptr<YSweep>> grp;
                 for (int l = 0; l < g; ++l)
                     grp.emplace_back(new YSweep(A, H, pd.P, m, seed, probe_offset + (s0 + l) * pd.P,
-                                                htrec + pd.rec * (s0 + l), l));
+                                                htrec + pd.rec * (s0 + l), l, int0));
                 for (auto& y : grp) y->start();
                 for (int j = 0; j + 1 < m; ++j)
                     for (auto& y : grp) y->step(j);

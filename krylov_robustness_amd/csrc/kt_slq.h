@@ -63,12 +63,25 @@ class ExplicitSweep {
     DevBuf* hist_dev = nullptr;
 };
 
+// Whether a sign-table-seeded y-form sweep of depth m may carry y_0 as int16
+// row sums: unit weights, so a row's start-pass sum is an
+// integer of magnitude <= its length, every row at most 32,767 long, and at
+// least one ordinary pass after the start (m >= 3; at m = 2 the only pass is
+// the half-gather last pass, which has no int16 variant).
+inline bool int0_applies(bool unit_values, int64_t max_row, int m) {
+    return unit_values && max_row <= 32767 && m >= 3;
+}
+
 // lanczos_sweep_y (the RNG-seeded y-form sweep of the Hutchinson hot path)
 // enqueued step by step: start(), step(j) for j < m - 1, finish().
+// int0: the compact form -- the start pass stores y_0 as an n x P int16 table
+// behind the sign table, the first step (k_spmm_lanczos_first) gathers it and
+// the second reads it as Yold; from the third step on nothing differs, and
+// every record is bit-identical to the fp64 form's.
 class YSweep {
    public:
     YSweep(kt_matrix_s* A, const DevCSR& M, int P, int m, uint64_t seed, int64_t probe_base, double* rec_host,
-           int lane);
+           int lane, bool int0 = false);
     void start();
     void step(int j);
     void finish();
@@ -88,6 +101,9 @@ class YSweep {
     double *part = nullptr, *ys = nullptr, *trec = nullptr, *guard = nullptr;
     uint32_t* Z = nullptr;
     double *Xc = nullptr, *Yo = nullptr, *Ot = nullptr;
+    bool int0 = false;
+    int16_t* T0 = nullptr;  // int0: y_0's row sums
+    double s0 = 0.0;        // 1 / ||z||
 };
 
 // lanczos_sweep_y_block enqueued step by step: start(), step(j) for j < m - 1,

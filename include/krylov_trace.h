@@ -100,6 +100,24 @@ int kt_slq_submit(kt_matrix_t A, int fun, int m, uint64_t seed, int64_t probe_of
                   int block, int* ticket);
 int kt_slq_collect(kt_matrix_t A, int ticket, double* sum_q, double* sum_q2, double* q);
 
+/* kt_slq_trace with an error-controlled depth: the same probes (seed,
+ * probe_offset, nprobes, block as above), each run until the stopping test
+ * of kt_lanczos_fmv_auto holds on its own tridiagonal (two consecutive
+ * agreements of the quadrature to rtol from depth 8 on, fun = KT_FUN_EXP
+ * scaled by exp(-theta_max); a beta < 1e-8 cuts the probe) or m_max rows are
+ * reached (m_max <= 0: 128; above 256: KT_ERR_ARG).  rtol <= 0: the default,
+ * 1e-12.  q_p is formed from probe p's record truncated at depth[p]; it
+ * depends only on (A, seed, p, block, m_max, rtol) and on whether its sweep
+ * was redone by the explicit sweep, as kt_slq_trace's does -- not on the
+ * other probes of its sweep or call, the lane, or timing.  A probe that
+ * reaches m_max unconverged is not an error: *capped counts them
+ * (kt_context_stat 6; stat 5 takes the largest depth).  depth (nprobes), q
+ * and capped are optional.  Blocking; refused while kt_slq_submit tickets
+ * are outstanding.  kt_slq_submit / kt_slq_collect stay fixed-depth. */
+int kt_slq_trace_auto(kt_matrix_t A, int fun, int m_max, double rtol, uint64_t seed, int64_t probe_offset,
+                      int64_t nprobes, int block, double* sum_q, double* sum_q2, double* q, int* depth,
+                      int64_t* capped);
+
 /* The probes-per-sweep width kt_slq_trace picks when block == 0. */
 int kt_slq_plan(kt_matrix_t A, int64_t nprobes, int* block);
 
@@ -355,7 +373,8 @@ int kt_eigs_leading(kt_matrix_t A, double tol, int maxit, double* lambda, double
  * sweep's passes in 0), 3 = the y-form pass of a sweep seeded
  * by a given block (k_spmm_lanczos in mc_trace's quadrature-only columns),
  * 4 = the expmv Taylor-term kernel (k_expmv_rows / k_expmv_step, one launch
- * per term; a term queued past its stage's stop is a short no-op launch).
+ * per term; a term queued past its stage's stop is a short no-op launch),
+ * 6 = the stopping test of kt_slq_trace_auto's sweeps (k_quad_check_wide).
  * Returns launch count and summed milliseconds. */
 int kt_profile_enable(kt_context_t ctx, int enable);
 int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* total_ms);
@@ -389,7 +408,9 @@ int kt_debug_delay(kt_context_t ctx, int lane, double microseconds);
  * columns that reached the depth cap unconverged, both since context
  * creation.  stat 7: kt_slq_trace y-form sweeps that carried y_0 as int16 row
  * sums (kt_host_int0_applies; KT_SLQ_INT0=0, read per call, turns the form
- * off), since context creation. */
+ * off), since context creation.  stat 8: y-form step passes queued by
+ * kt_slq_trace_auto calls (those queued past a sweep's last stop, which
+ * return at once, included), since context creation. */
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value);
 
 /* Threads of the process-wide host pool (the per-column / per-candidate

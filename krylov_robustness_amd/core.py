@@ -85,7 +85,8 @@ class Context:
         fallbacks, 2 basis columns of the last fun_update, 3 expmv calls,
         4 Taylor terms those calls executed, 5 the largest depth the adaptive
         Lanczos Afun used, 6 its columns that reached the depth cap, 7 y-form
-        sweeps that carried y_0 as int16 row sums."""
+        sweeps that carried y_0 as int16 row sums, 8 y-form step passes queued
+        by slq_quadforms_auto."""
         v = C.c_int64()
         _lib.check(_lib.load().kt_context_stat(self._h, int(which), C.byref(v)))
         return int(v.value)
@@ -253,6 +254,39 @@ def slq_trace(A, nprobes: int, m: int, seed: int = 0, fun="exp", block: int = 0,
               ctx: Optional[Context] = None):
     """Plain-Hutchinson trace(f(A)) estimate with Lanczos quadrature."""
     s1, _, q = slq_quadforms(A, nprobes, m, seed, fun, 0, block, ctx)
+    return s1 / max(nprobes, 1), q
+
+
+def slq_quadforms_auto(A, nprobes: int, m_max: int = 128, rtol=None, seed: int = 0, fun="exp",
+                       probe_offset: int = 0, block: int = 0, return_info: bool = False,
+                       ctx: Optional[Context] = None):
+    """slq_quadforms with an error-controlled depth (kt_slq_trace_auto): each
+    probe runs until its own quadrature agrees twice in a row to rtol (from
+    depth 8 on; default 1e-12) or m_max rows (<= 256) are reached, and its
+    form comes from its record truncated there.  Returns (sum, sum_sq, q);
+    with return_info also {"depth": steps per probe, "capped": probes that
+    reached m_max unconverged}."""
+    D = _dev(A, ctx)
+    nprobes = int(nprobes)
+    q = np.zeros(max(nprobes, 1), dtype=np.float64)
+    depth = np.zeros(max(nprobes, 1), dtype=np.int32)
+    s1 = C.c_double()
+    s2 = C.c_double()
+    capped = C.c_int64()
+    _lib.check(_lib.load().kt_slq_trace_auto(
+        D.handle, _fun_code(fun), int(m_max), float(rtol) if rtol is not None else 0.0,
+        int(seed) & 0xFFFFFFFFFFFFFFFF, int(probe_offset), nprobes, int(block), C.byref(s1), C.byref(s2),
+        q.ctypes.data_as(C.POINTER(C.c_double)), depth.ctypes.data_as(C.POINTER(C.c_int)), C.byref(capped)))
+    out = (float(s1.value), float(s2.value), q[:nprobes])
+    if return_info:
+        return out + ({"depth": depth[:nprobes].astype(np.int64), "capped": int(capped.value)},)
+    return out
+
+
+def slq_trace_auto(A, nprobes: int, m_max: int = 128, rtol=None, seed: int = 0, fun="exp", block: int = 0,
+                   ctx: Optional[Context] = None):
+    """Plain-Hutchinson trace(f(A)) estimate with the error-controlled depth."""
+    s1, _, q = slq_quadforms_auto(A, nprobes, m_max, rtol, seed, fun, 0, block, False, ctx)
     return s1 / max(nprobes, 1), q
 
 

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 
 #include "kt_internal.h"
 #include "kt_launch.h"
@@ -93,6 +94,87 @@ __device__ void dev_ql_rows(int m, int G, double* d, double* e, double* z, doubl
     }
 }
 
+// One column's stopping test at depth j (lane t of G owns column c; the LDS
+// arrays sm are [k][lane] with stride G): the body of k_quad_check and
+// k_quad_check_wide.  Returns whether the column is stopped after it.
+// guard / gmin / gsnap: k_quad_check_wide's guard argument (nullptr: none).
+__device__ __forceinline__ int dev_check_column(const double* __restrict__ trec, int mcap, int P, int j, int c,
+                                                int t, int G, int nfe, const double* __restrict__ n2, int fun,
+                                                double rtol, double* __restrict__ state, double* sm,
+                                                const double* __restrict__ guard, double gmin,
+                                                double* __restrict__ gsnap) {
+    int stopped;
+    double* st = state + (size_t)c * kAdaptState;
+    stopped = st[4] != 0.0;
+    if (!stopped && n2 && !(n2[c] > 0.0)) {
+        st[0] = 0.0;
+        st[3] = 0.0;
+        st[4] = 1.0;
+        stopped = 1;
+        if (guard) gsnap[c] = 1.0;
+    } else if (!stopped && guard && !(guard[c] >= gmin)) {
+        st[3] = (double)j;
+        st[4] = 1.0;
+        stopped = 1;
+        gsnap[c] = guard[c];
+    } else if (!stopped) {
+        const double* al = trec + c;
+        const double* up = trec + (size_t)mcap * P + c;
+        const double* low = trec + (size_t)2 * mcap * P + c;
+        int steps = j;
+        bool broke = false;
+        for (int k = 0; k < j; ++k)
+            if (low[(size_t)k * P] < 1e-8) {
+                steps = k + 1;
+                broke = true;
+                break;
+            }
+        double* d = sm + t;
+        double* e = sm + (size_t)j * G + t;
+        double* z = sm + (size_t)2 * j * G + t;
+        double* zl = sm + (size_t)3 * j * G + t;
+        for (int k = 0; k < steps; ++k) d[k * G] = al[(size_t)k * P];
+        for (int k = 0; k + 1 < steps; ++k) e[k * G] = 0.5 * (low[(size_t)k * P] + up[(size_t)(k + 1) * P]);
+        const bool wf = c < nfe && !broke;
+        if (wf)
+            dev_ql_rows<true>(steps, G, d, e, z, zl);
+        else
+            dev_ql_rows<false>(steps, G, d, e, z, zl);
+        double tm = d[0];
+        for (int k = 1; k < steps; ++k) tm = fmax(tm, d[k * G]);
+        const double shift = (fun == KT_FUN_EXP) ? tm : 0.0;
+        double q = 0.0, lastc = 0.0, nrm2 = 0.0;
+        for (int k = 0; k < steps; ++k) {
+            const double w = dev_fscalar(fun, d[k * G] - shift), z1 = z[k * G];
+            q += z1 * z1 * w;
+            if (wf) lastc += zl[k * G] * z1 * w;
+            nrm2 += z1 * z1 * w * w;
+        }
+        const bool hist = st[7] == (double)(j - 1);
+        const double q1 = st[0];
+        // theta_max grows with the depth: the shallower sum at this depth's scale
+        const double q1s = (fun == KT_FUN_EXP) ? q1 * exp(st[5] - tm) : q1;
+        const bool agree1 = hist && fabs(q - q1s) <= rtol * fabs(q);
+        const bool agree2 = hist && st[6] != 0.0;
+        bool stop = broke;
+        if (!stop && j >= kAdaptMinDepth && agree1 && agree2)
+            stop = !wf || low[(size_t)(j - 1) * P] * fabs(lastc) <= rtol * sqrt(nrm2);
+        st[2] = st[1];
+        st[1] = q1;
+        st[0] = q;
+        st[5] = tm;
+        st[6] = agree1 ? 1.0 : 0.0;
+        st[7] = (double)j;
+        if (stop) {
+            st[3] = (double)steps;
+            st[4] = 1.0;
+            stopped = 1;
+            if (guard) gsnap[c] = guard[c];
+        }
+    }
+    return stopped;
+}
+
 }  // namespace
 
 // The stopping test of the adaptive depth at depth j: one workgroup of one
@@ -118,69 +200,8 @@ __global__ __launch_bounds__(64) void k_quad_check(const double* __restrict__ tr
     const int t = threadIdx.x, c = g0 + t;
     const bool mine = t < G && c < live;
     int stopped = -1;
-    if (mine) {
-        double* st = state + (size_t)c * kAdaptState;
-        stopped = st[4] != 0.0;
-        if (!stopped && n2 && !(n2[c] > 0.0)) {
-            st[0] = 0.0;
-            st[3] = 0.0;
-            st[4] = 1.0;
-            stopped = 1;
-        } else if (!stopped) {
-            const double* al = trec + c;
-            const double* up = trec + (size_t)mcap * P + c;
-            const double* low = trec + (size_t)2 * mcap * P + c;
-            int steps = j;
-            bool broke = false;
-            for (int k = 0; k < j; ++k)
-                if (low[(size_t)k * P] < 1e-8) {
-                    steps = k + 1;
-                    broke = true;
-                    break;
-                }
-            double* d = sm + t;
-            double* e = sm + (size_t)j * G + t;
-            double* z = sm + (size_t)2 * j * G + t;
-            double* zl = sm + (size_t)3 * j * G + t;
-            for (int k = 0; k < steps; ++k) d[k * G] = al[(size_t)k * P];
-            for (int k = 0; k + 1 < steps; ++k) e[k * G] = 0.5 * (low[(size_t)k * P] + up[(size_t)(k + 1) * P]);
-            const bool wf = c < nfe && !broke;
-            if (wf)
-                dev_ql_rows<true>(steps, G, d, e, z, zl);
-            else
-                dev_ql_rows<false>(steps, G, d, e, z, zl);
-            double tm = d[0];
-            for (int k = 1; k < steps; ++k) tm = fmax(tm, d[k * G]);
-            const double shift = (fun == KT_FUN_EXP) ? tm : 0.0;
-            double q = 0.0, lastc = 0.0, nrm2 = 0.0;
-            for (int k = 0; k < steps; ++k) {
-                const double w = dev_fscalar(fun, d[k * G] - shift), z1 = z[k * G];
-                q += z1 * z1 * w;
-                if (wf) lastc += zl[k * G] * z1 * w;
-                nrm2 += z1 * z1 * w * w;
-            }
-            const bool hist = st[7] == (double)(j - 1);
-            const double q1 = st[0];
-            // theta_max grows with the depth: the shallower sum at this depth's scale
-            const double q1s = (fun == KT_FUN_EXP) ? q1 * exp(st[5] - tm) : q1;
-            const bool agree1 = hist && fabs(q - q1s) <= rtol * fabs(q);
-            const bool agree2 = hist && st[6] != 0.0;
-            bool stop = broke;
-            if (!stop && j >= kAdaptMinDepth && agree1 && agree2)
-                stop = !wf || low[(size_t)(j - 1) * P] * fabs(lastc) <= rtol * sqrt(nrm2);
-            st[2] = st[1];
-            st[1] = q1;
-            st[0] = q;
-            st[5] = tm;
-            st[6] = agree1 ? 1.0 : 0.0;
-            st[7] = (double)j;
-            if (stop) {
-                st[3] = (double)steps;
-                st[4] = 1.0;
-                stopped = 1;
-            }
-        }
-    }
+    if (mine)
+        stopped = dev_check_column(trec, mcap, P, j, c, t, G, nfe, n2, fun, rtol, state, sm, nullptr, 0.0, nullptr);
     stopped_l[t] = stopped;
     __syncthreads();
     if (t == 0) {
@@ -208,6 +229,73 @@ hipError_t launch_quad_check(const double* trec, int mcap, int P, int j, int liv
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// k_quad_check for any sweep width (the SLQ sweeps, kt_slq.cpp
+// slq_trace_auto): workgroup b owns columns [16 b, 16 b + 16), lane t column
+// 16 b + t, with the same per-column test, state layout and [k][lane] LDS
+// arrays (G = 16: 512 j bytes).  running[b]: workgroup b's columns still
+// running -- its own columns only, an ordinary store by lane 0, so no
+// workgroup reads another's state and the sweep's running words are the
+// grid's ceil(live / 16) counts (the gate of the step launches ORs them).
+// guard (nullable; the y-form sweep's running guard value per column): a
+// running column whose guard is not >= gmin stops at once, flagged with its
+// depth (its sweep is redone by the explicit sweep whatever it decides); a
+// column that stops leaves the guard it stopped with in gsnap[c], the value
+// the host judges the sweep by, so the verdict does not depend on how many
+// steps ran past the column's depth.
+__global__ __launch_bounds__(64) void k_quad_check_wide(const double* __restrict__ trec, int mcap, int P, int j,
+                                                        int live, int nfe, const double* __restrict__ n2, int fun,
+                                                        double rtol, double* __restrict__ state,
+                                                        int* __restrict__ running,
+                                                        const double* __restrict__ guard, double gmin,
+                                                        double* __restrict__ gsnap) {
+    extern __shared__ double sm[];
+    __shared__ int stopped_l[kWideCheckCols];
+    constexpr int G = kWideCheckCols;
+    const int t = threadIdx.x, c = blockIdx.x * G + t;
+    const bool mine = t < G && c < live;
+    int stopped = -1;
+    if (mine) stopped = dev_check_column(trec, mcap, P, j, c, t, G, nfe, n2, fun, rtol, state, sm, guard, gmin, gsnap);
+    if (t < G) stopped_l[t] = stopped;
+    __syncthreads();
+    if (t == 0) {
+        int run = 0;
+        for (int k = 0; k < G; ++k) run += stopped_l[k] == 0;
+        running[blockIdx.x] = run;
+    }
+}
+
+// 1 <= live <= P <= 128, 1 <= j <= mcap <= 256: one launch of ceil(live / 16)
+// workgroups per check.  512 j bytes of LDS per workgroup: from 64 KB on (j >= 128)
+// the kernel opts in to the large dynamic LDS (128 KB at j = 256 of the 160 KB
+// a gfx950 workgroup may declare).
+hipError_t launch_quad_check_wide(const double* trec, int mcap, int P, int j, int live, int nfe, const double* n2,
+                                  int fun, double rtol, double* state, int* running, hipStream_t st,
+                                  const double* guard, double gmin, double* gsnap) {
+    if (P < 1 || P > 128 || live < 1 || live > P || j < 1 || j > mcap || mcap > 256) return hipErrorInvalidValue;
+    if (guard && !gsnap) return hipErrorInvalidValue;
+    const size_t lds = sizeof(double) * 4 * (size_t)j * kWideCheckCols;
+    // with the kernel's static stopped_l the workgroup passes 64 KB from j = 128 on;
+    // the opt-in is per device and made once for each
+    if (lds + sizeof(int) * kWideCheckCols > (size_t)65536) {
+        static std::atomic<uint64_t> opted{0};
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return e;
+        const uint64_t bit = (dev >= 0 && dev < 64) ? (uint64_t)1 << dev : 0;
+        if (!bit || !(opted.load(std::memory_order_acquire) & bit)) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_quad_check_wide),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(sizeof(double) * 4 * 256 * kWideCheckCols));
+            if (e != hipSuccess) return e;
+            opted.fetch_or(bit, std::memory_order_release);
+        }
+    }
+    const int grid = (live + kWideCheckCols - 1) / kWideCheckCols;
+    k_quad_check_wide<<<grid, 64, lds, st>>>(trec, mcap, P, j, live, nfe, n2, fun, rtol, state, running, guard,
+                                             gmin, gsnap);
+    return hipGetLastError();
 }
 
 // Y[r, c] = sum_{j < m} U_j[r * nc + c] W[j * nc + c], slot j (n x nc,

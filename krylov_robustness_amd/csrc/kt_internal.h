@@ -134,10 +134,11 @@ struct ProfSlot {
 };
 
 // PROF_FIRST: the compact sweep's first step (k_spmm_lanczos_first) alone; the
-// launch is also one of the sweep's step passes in PROF_SPMM
+// launch is also one of the sweep's step passes in PROF_SPMM.  PROF_CHECK:
+// the stopping test of an error-controlled SLQ sweep (k_quad_check_wide)
 enum {
     PROF_SPMM = 0, PROF_UPDATE = 1, PROF_START = 2, PROF_YBLOCK = 3, PROF_EXPMV = 4, PROF_FIRST = 5,
-    PROF_NSLOTS = 6
+    PROF_CHECK = 6, PROF_NSLOTS = 7
 };
 
 // Buffers of one probe-sweep lane (kt_slq.cpp); two lanes let two sweeps
@@ -224,6 +225,12 @@ struct Workspace {
     // still-active columns), the pinned words the host polls and their events
     DevBuf adapt_state[4];
     PinnedBuf pin_adapt;
+    // kt_slq_trace_auto: per lane the check's device block (state, guard
+    // snapshot, running words), the ring of polled copies and their events
+    DevBuf auto_state[4];
+    PinnedBuf pin_auto, pin_auto_rec;
+    hipEvent_t auto_ev[4][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr},
+                                {nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
     hipEvent_t adapt_ev[4][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
 };
 
@@ -247,6 +254,7 @@ struct kt_context_s {
     int64_t adapt_max_depth = 0;  // adaptive Lanczos Afun: the largest depth a column used
     int64_t adapt_capped = 0;     // ... and its columns that reached the depth cap unconverged
     int64_t int0_sweeps = 0;      // y-form sweeps that carried y_0 as int16 row sums (kt_slq.h int0_applies)
+    int64_t auto_passes = 0;      // y-form step passes queued by kt_slq_trace_auto calls (gated ones included)
     int ky_flags = 8;   // y-form pass flags (8 = nontemporal store of y_{j+1}, +0.3 %)
     bool yform = true;  // KT_SLQ_YFORM=0: the hot path runs the explicit K1/K2 sweep
     void* blas = nullptr;  // rocblas_handle, created on first block-Krylov use

@@ -93,9 +93,21 @@ template <int P> using GeoB = GeoW<P, (P >= 16) ? kBlkVW : (P >= 2) ? 2 : 1>;
 // basis of f(A) x = ||x|| V f(T) e1) from the pass's own rows.
 // FLAGS bit 7 (k_spmm_lanczos, a compact sweep's second step): Yold = y_0 is
 // the start pass's n x P int16 table, read as s0 * (double)k (ld_i16).
+// FLAGS bit 8 (k_spmm_lanczos, k_spmm_lanczos_first): the gated form of an
+// error-controlled sweep -- the launch returns at once, writing nothing, when
+// the sweep's running words (gate[0 .. ngate)) all read zero.
 enum : int {
-    KF_NT = 1, KF_UNIT = 2, KF_MLP = 4, KF_NTY = 8, KF_SC1 = 16, KF_MU0 = 32, KF_VB = 64, KF_I16 = 128
+    KF_NT = 1, KF_UNIT = 2, KF_MLP = 4, KF_NTY = 8, KF_SC1 = 16, KF_MU0 = 32, KF_VB = 64, KF_I16 = 128,
+    KF_GATE = 256
 };
+
+// Whether a gated launch runs: any of the sweep's running words non-zero
+// (uniform over the grid; a stale non-zero word only runs one more step).
+__device__ __forceinline__ bool gate_open(const int* __restrict__ gate, int ngate) {
+    int run = 0;
+    for (int k = 0; k < ngate; ++k) run |= gate[k];
+    return run != 0;
+}
 
 typedef unsigned int kt_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int kt_u32x2 __attribute__((ext_vector_type(2)));
@@ -767,7 +779,9 @@ __global__ __launch_bounds__(BLOCK) void k_spmm_lanczos(
     const double* __restrict__ coef, double* __restrict__ partial,
     const int* __restrict__ long_rows, int n_long, int long_thresh, int long_blocks,
     const double* __restrict__ Vc, const double* __restrict__ Vo, double* __restrict__ Vn, int bcols,
-    double s0) {
+    double s0, const int* __restrict__ gate, int ngate) {
+    if constexpr (FLAGS & KF_GATE)
+        if (!gate_open(gate, ngate)) return;
     using G = GeoKY<P>;
     constexpr int WAVES = BLOCK / 64;
     const int lane = threadIdx.x & 63;
@@ -893,7 +907,10 @@ template <int P, int BLOCK, int FLAGS>
 __global__ __launch_bounds__(BLOCK) void k_spmm_lanczos_first(
     const int* __restrict__ row_ptr, const int* __restrict__ col, int n, const int16_t* __restrict__ T,
     double s0, double* __restrict__ Out, const double* __restrict__ coef, double* __restrict__ partial,
-    const int* __restrict__ long_rows, int n_long, int long_thresh, int long_blocks) {
+    const int* __restrict__ long_rows, int n_long, int long_thresh, int long_blocks,
+    const int* __restrict__ gate, int ngate) {
+    if constexpr (FLAGS & KF_GATE)
+        if (!gate_open(gate, ngate)) return;
     using G = GeoKY<P>;
     using V = VecT<G::VEC>;
     constexpr int WAVES = BLOCK / 64;
@@ -1405,14 +1422,19 @@ __global__ __launch_bounds__(256) void k_norm(const double* __restrict__ partial
 // explicit CGS2 path on the host (kt_slq.cpp), so breakdowns keep the
 // reference's semantics (lanczos_krylov.m:91-93).
 // Records: alpha[j], up[j] = beta_j, low[j] = beta_{j+1}.
-template <int P>
+// GATE: the gated form (gate_open above): nothing is read or written when the
+// sweep's running words all read zero.
+template <int P, bool GATE = false>
 __global__ __launch_bounds__(192) void k_ycoef(const double* __restrict__ partial, int nblk,
                                                int start, int last, double s0,
                                                double* __restrict__ ys,
                                                double* __restrict__ t_alpha,
                                                double* __restrict__ t_up,
                                                double* __restrict__ t_low,
-                                               double* __restrict__ guard) {
+                                               double* __restrict__ guard,
+                                               const int* __restrict__ gate, int ngate) {
+    if constexpr (GATE)
+        if (!gate_open(gate, ngate)) return;
     const int p = blockIdx.x;
     const int q = threadIdx.x >> 6;
     const double r = wave_reduce_slot(partial, nblk, q * P + p);
@@ -2551,13 +2573,20 @@ hipError_t launch_spmm_lanczos(int P, int flags, int grid, const int* rp, const 
                                double* Out, const double* coef, double* partial,
                                const int* long_rows, int n_long, int long_thresh, int long_blocks,
                                hipStream_t st, const double* Vc, const double* Vo, double* Vn, int bcols,
-                               double s0) {
+                               double s0, const int* gate, int ngate) {
+    if (gate && (Vn || ngate < 1 || ngate > kGateWordsMax)) return hipErrorInvalidValue;
     return dispatch_p(P, [&](auto c) {
         constexpr int PP = decltype(c)::value;
 #define KT_KY(F)                                                                                   \
     k_spmm_lanczos<PP, kBlock, F><<<grid, kBlock, 0, st>>>(rp, ci, va, n, X, Yold, Out, coef, partial, \
                                                            long_rows, n_long, long_thresh, long_blocks, \
-                                                           Vc, Vo, Vn, bcols, s0)
+                                                           Vc, Vo, Vn, bcols, s0, gate, ngate)
+        if (gate) {  // an error-controlled sweep's pass: forms only, y_{j+1} stored nontemporal
+            if (flags & KF_I16) KT_KY(KF_UNIT | KF_I16 | KF_NTY | KF_GATE);
+            else if (flags & KF_UNIT) KT_KY(KF_UNIT | KF_NTY | KF_GATE);
+            else KT_KY(KF_NTY | KF_GATE);
+            return;
+        }
         if (flags & KF_I16) {  // a compact sweep's second step (unit weights, no basis): Yold = int16 y_0
             if (flags & KF_SC1) KT_KY(KF_UNIT | KF_I16 | KF_SC1);
             else if (flags & KF_NTY) KT_KY(KF_UNIT | KF_I16 | KF_NTY);
@@ -2650,14 +2679,16 @@ hipError_t launch_spmm_lanczos_start(int P, int flags, int grid, const int* rp, 
 hipError_t launch_spmm_lanczos_first(int P, int flags, int grid, const int* rp, const int* ci, int n,
                                      const int16_t* T, double s0, double* Out, const double* coef,
                                      double* partial, const int* long_rows, int n_long, int long_thresh,
-                                     int long_blocks, hipStream_t st) {
+                                     int long_blocks, hipStream_t st, const int* gate, int ngate) {
+    if (gate && (ngate < 1 || ngate > kGateWordsMax)) return hipErrorInvalidValue;
     return dispatch_p(P, [&](auto c) {
         constexpr int PP = decltype(c)::value;
 #define KT_KF(F)                                                                                  \
     k_spmm_lanczos_first<PP, kBlock, F><<<grid, kBlock, 0, st>>>(rp, ci, n, T, s0, Out, coef, partial, \
                                                                  long_rows, n_long, long_thresh,   \
-                                                                 long_blocks)
-        if (flags & KF_SC1) KT_KF(KF_UNIT | KF_SC1);
+                                                                 long_blocks, gate, ngate)
+        if (gate) KT_KF(KF_UNIT | KF_NTY | KF_GATE);
+        else if (flags & KF_SC1) KT_KF(KF_UNIT | KF_SC1);
         else if (flags & KF_NTY) KT_KF(KF_UNIT | KF_NTY);
         else KT_KF(KF_UNIT);
 #undef KT_KF
@@ -2666,11 +2697,16 @@ hipError_t launch_spmm_lanczos_first(int P, int flags, int grid, const int* rp, 
 
 hipError_t launch_ycoef(int P, const double* partial, int nblk, int start, int last, double s0,
                         double* ys, double* t_alpha, double* t_up, double* t_low, double* guard,
-                        hipStream_t st) {
+                        hipStream_t st, const int* gate, int ngate) {
+    if (gate && (ngate < 1 || ngate > kGateWordsMax)) return hipErrorInvalidValue;
     return dispatch_p(P, [&](auto c) {
         constexpr int PP = decltype(c)::value;
-        k_ycoef<PP><<<PP, 192, 0, st>>>(partial, nblk, start, last, s0, ys, t_alpha, t_up, t_low,
-                                        guard);
+        if (gate)
+            k_ycoef<PP, true><<<PP, 192, 0, st>>>(partial, nblk, start, last, s0, ys, t_alpha, t_up, t_low, guard,
+                                                  gate, ngate);
+        else
+            k_ycoef<PP><<<PP, 192, 0, st>>>(partial, nblk, start, last, s0, ys, t_alpha, t_up, t_low,
+                                            guard, nullptr, 0);
     });
 }
 

@@ -90,19 +90,25 @@ hipError_t launch_norm(int P, const double* partial, int nblk, double* k2s, doub
 // from slots Vc (v_j) and Vo (v_{j-1}, nullptr at j = 0), columns < bcols
 // (every slot n x P, row-major).  flags bit 7 (a compact sweep's second
 // step; unit weights, no basis): Yold is the start pass's n x P int16 table,
-// y_0 = s0 * (double)Yold
+// y_0 = s0 * (double)Yold.
+// gate (nullable; ngate <= kGateWordsMax words): the gated form of an
+// error-controlled sweep (kt_slq.cpp slq_trace_auto) -- when every word reads
+// zero each workgroup returns at once and nothing is written; bits as the
+// ungated launch otherwise (forms-only passes; y_{j+1} stored nontemporal)
 hipError_t launch_spmm_lanczos(int P, int flags, int grid, const int* rp, const int* ci,
                                const double* va, int n, const double* X, const double* Yold,
                                double* Out, const double* coef, double* partial,
                                const int* long_rows, int n_long, int long_thresh, int long_blocks,
                                hipStream_t st, const double* Vc = nullptr, const double* Vo = nullptr,
-                               double* Vn = nullptr, int bcols = 0, double s0 = 0.0);
+                               double* Vn = nullptr, int bcols = 0, double s0 = 0.0,
+                               const int* gate = nullptr, int ngate = 0);
 // First ordinary step of a compact sweep (unit weights): launch_spmm_lanczos
 // with X = y_0 = s0 * (double)T read from the int16 table T and no Yold
 hipError_t launch_spmm_lanczos_first(int P, int flags, int grid, const int* rp, const int* ci, int n,
                                      const int16_t* T, double s0, double* Out, const double* coef,
                                      double* partial, const int* long_rows, int n_long, int long_thresh,
-                                     int long_blocks, hipStream_t st);
+                                     int long_blocks, hipStream_t st, const int* gate = nullptr,
+                                     int ngate = 0);
 // The last pass of a y-form sweep: only slab 0, X'A X per probe, from each
 // row's strictly-lower prefix and diagonal (lower = DevCSR::lower; slabs 1, 2
 // are written as zeros).  Vn as above.
@@ -122,7 +128,7 @@ hipError_t launch_spmm_lanczos_start(int P, int flags, int grid, const int* rp, 
                                      int long_thresh, int long_blocks, hipStream_t st);
 hipError_t launch_ycoef(int P, const double* partial, int nblk, int start, int last, double s0,
                         double* ys, double* t_alpha, double* t_up, double* t_low, double* guard,
-                        hipStream_t st);
+                        hipStream_t st, const int* gate = nullptr, int ngate = 0);
 // the adaptive Lanczos depth (kt_adapt.hip): the stopping test at depth j on a
 // sweep's device record [alpha | up | low][mcap][P] (state: kAdaptState
 // doubles per column, zeroed before the sweep's first check; the checks of a
@@ -135,6 +141,17 @@ struct SlotTab {
 };
 hipError_t launch_quad_check(const double* trec, int mcap, int P, int j, int live, int nfe, const double* n2,
                              int fun, double rtol, double* state, int* active, hipStream_t st);
+// The same test for any sweep width, P <= 128 and depths <= 256, one launch
+// per check: workgroup b owns columns [16 b, 16 b + 16) and stores the count
+// of its own running columns to running[b], b < ceil(live / 16) (the words a
+// gated step launch reads).  guard (nullable, with gsnap): the y-form sweep's
+// guard values; a column whose guard is not >= gmin stops at once, and every
+// column that stops leaves the guard it stopped with in gsnap[c].
+constexpr int kWideCheckCols = 16;
+constexpr int kGateWordsMax = 128 / kWideCheckCols;
+hipError_t launch_quad_check_wide(const double* trec, int mcap, int P, int j, int live, int nfe, const double* n2,
+                                  int fun, double rtol, double* state, int* running, hipStream_t st,
+                                  const double* guard = nullptr, double gmin = 0.0, double* gsnap = nullptr);
 hipError_t launch_weighted_sum_tab(int n, int m, int nc, const SlotTab& tab, int spc, const double* W, double* Y,
                                    int ldy, hipStream_t st);
 hipError_t launch_fill(double* x, int count, double v, hipStream_t st);

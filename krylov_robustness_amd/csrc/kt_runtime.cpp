@@ -466,6 +466,9 @@ int kt_context_destroy(kt_context_t ctx) {
     for (auto& lane : w.adapt_ev)
         for (auto& e : lane)
             if (e) (void)hipEventDestroy(e);
+    for (auto& lane : w.auto_ev)
+        for (auto& e : lane)
+            if (e) (void)hipEventDestroy(e);
     for (auto& b : w.host_trec) b.release();
     for (auto& pd : w.slq_pend)
         for (auto& e : pd.done)
@@ -605,9 +608,10 @@ int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* tot
 
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value) {
     KT_GUARD_BEGIN
-    if (!ctx || !value || stat < 0 || stat > 7) fail(KT_ERR_ARG, "bad stat query");
-    const int64_t v[8] = {ctx->yform_redone, ctx->fu_dense, ctx->fu_last_cols, ctx->expmv_calls,
-                          ctx->expmv_terms, ctx->adapt_max_depth, ctx->adapt_capped, ctx->int0_sweeps};
+    if (!ctx || !value || stat < 0 || stat > 8) fail(KT_ERR_ARG, "bad stat query");
+    const int64_t v[9] = {ctx->yform_redone, ctx->fu_dense, ctx->fu_last_cols, ctx->expmv_calls,
+                          ctx->expmv_terms, ctx->adapt_max_depth, ctx->adapt_capped, ctx->int0_sweeps,
+                          ctx->auto_passes};
     *value = v[stat];
     KT_GUARD_END
 }

@@ -185,9 +185,9 @@ void lanczos_sweep(kt_matrix_s* A, const DevCSR& M, int P, int m, uint64_t seed,
 // step by step (start(), step(j) for j < m - 1, finish()), so sweeps on
 // different lanes are queued launch by launch.
 YSweep::YSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, uint64_t seed_, int64_t probe_base_,
-               double* rec_host_, int lane_, bool int0_)
+               double* rec_host_, int lane_, bool int0_, const int* gate_, int ngate_)
     : A(A_), M(M_), P(P_), m(m_), seed(seed_), probe_base(probe_base_), rec_host(rec_host_), lane(lane_),
-      int0(int0_) {
+      int0(int0_), gate(gate_), ngate(ngate_) {
     kt_context_s* ctx = A->ctx;
     n = (int)A->n;
     if (lane < 0 || lane > 3) fail(KT_ERR_ARG, "sweep lane out of range");
@@ -236,17 +236,21 @@ void YSweep::start() {
                                      int0 ? reinterpret_cast<double*>(T0) : Xc, part, M.long_rows, M.n_long,
                                      A->long_thresh, lblocks, st));
     prof_end(ctx, PROF_START, st);
-    KT_HIP(launch_ycoef(P, part, grid1, 1, m == 1, s0, ys, rec_at(0, 0), rec_at(1, 0), rec_at(2, 0), guard, st));
+    KT_HIP(launch_ycoef(P, part, grid1, 1, !gate && m == 1, s0, ys, rec_at(0, 0), rec_at(1, 0), rec_at(2, 0), guard,
+                        st));
 }
 
 void YSweep::step(int j) {
     kt_context_s* ctx = A->ctx;
     prof_begin(ctx, PROF_SPMM, st, P);
-    const bool last = j + 2 == m;  // y_{m} is never used: alpha_{m-1} needs only X'A X
+    // y_{m} is never used: alpha_{m-1} needs only X'A X (the resumable form
+    // has no last pass: every row it writes is complete)
+    const bool last = !gate && j + 2 == m;
+    if (gate) ctx->auto_passes += 1;
     if (int0 && j == 0) {  // m >= 3: never the last pass; also timed alone in its own slot
         prof_begin(ctx, PROF_FIRST, st, P);
         KT_HIP(launch_spmm_lanczos_first(P, flags, grid1, M.rowptr, M.col, n, T0, s0, Ot, ys + 6 * P, part,
-                                         M.long_rows, M.n_long, A->long_thresh, lblocks, st));
+                                         M.long_rows, M.n_long, A->long_thresh, lblocks, st, gate, ngate));
         prof_end(ctx, PROF_FIRST, st);
     } else if (last)
         KT_HIP(launch_spmm_quadform(P, flags, grid1, M.rowptr, M.col, M.val, M.lower, n, Xc, ys + 6 * P, part,
@@ -254,13 +258,15 @@ void YSweep::step(int j) {
     else if (int0 && j == 1)  // Yold = y_0 from the int16 table
         KT_HIP(launch_spmm_lanczos(P, flags | 128, grid1, M.rowptr, M.col, M.val, n, Xc,
                                    reinterpret_cast<const double*>(T0), Ot, ys + 6 * P, part, M.long_rows,
-                                   M.n_long, A->long_thresh, lblocks, st, nullptr, nullptr, nullptr, 0, s0));
+                                   M.n_long, A->long_thresh, lblocks, st, nullptr, nullptr, nullptr, 0, s0, gate,
+                                   ngate));
     else
         KT_HIP(launch_spmm_lanczos(P, flags, grid1, M.rowptr, M.col, M.val, n, Xc, Yo, Ot, ys + 6 * P, part,
-                                   M.long_rows, M.n_long, A->long_thresh, lblocks, st));
+                                   M.long_rows, M.n_long, A->long_thresh, lblocks, st, nullptr, nullptr, nullptr, 0,
+                                   0.0, gate, ngate));
     prof_end(ctx, PROF_SPMM, st);
     KT_HIP(launch_ycoef(P, part, grid1, 0, last, 0.0, ys, rec_at(0, j + 1), rec_at(1, j + 1), rec_at(2, j + 1),
-                        guard, st));
+                        guard, st, gate, ngate));
     Yo = Xc;  // y_{j+1} overwrites y_{j-1} from the next pass on
     Xc = Ot;
     Ot = Yo;
@@ -268,6 +274,14 @@ void YSweep::step(int j) {
 
 void YSweep::finish() {
     KT_HIP(hipMemcpyAsync(rec_host, trec, sizeof(double) * ((size_t)3 * m * P + P), hipMemcpyDeviceToHost, st));
+}
+
+void YSweep::finish(int rows) {
+    // the three record blocks' first `rows` rows, at the capacity's stride, and the guard
+    if (rows > 0)
+        KT_HIP(hipMemcpy2DAsync(rec_host, sizeof(double) * (size_t)m * P, trec, sizeof(double) * (size_t)m * P,
+                                sizeof(double) * (size_t)rows * P, 3, hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(rec_host + (size_t)3 * m * P, guard, sizeof(double) * P, hipMemcpyDeviceToHost, st));
 }
 
 // y-form sweep seeded by a given device block (the quadrature-only columns
@@ -1042,6 +1056,325 @@ static void slq_collect(kt_matrix_s* A, int ticket, double* sum_q, double* sum_q
     if (sum_q2) *sum_q2 = s2;
 }
 
+// ---- the error-controlled probe sweeps (kt_slq_trace_auto) ----
+//
+// The probe range of kt_slq_trace with each probe's depth chosen by the
+// stopping rule of lanczos_columns_adaptive, on resumable y-form sweeps.  The
+// check of depth j + 2 (k_quad_check_wide) is queued in the sweep's own stream
+// behind step j, so a column's depth is the first depth at which the rule
+// holds and the guard value it is judged by is the one it stopped with:
+// neither depends on what the host saw or when.  Every kAutoPoll depths the
+// sweep's running words are copied to a pinned ring slot behind an event; the
+// host reads finished polls without waiting and waits only for the oldest
+// when all kAutoRing slots are in flight, so at most
+// kAutoPoll kAutoRing + 1 = 9 step passes are queued past the check that
+// stopped a sweep's last column, and those are gated: they return at once.
+// The lanes run independently: a lane whose sweep has stopped (or reached its
+// last step) starts the call's next sweep at once.
+//
+// The y-form is measured to depth 100 (its Gram identities and guard,
+// DESIGN.md §4.1): a y-form sweep runs to min(m_max, kAutoHorizon) rows; with
+// columns still running there and m_max beyond, the whole sweep is handed to
+// the explicit CGS2 sweep (RNG-seeded at the same P, the test after every
+// step up to m_max), as is a sweep with a guarded column.
+constexpr int kAutoHorizon = 100, kAutoPoll = 2, kAutoRing = 4, kAutoFirstCheck = kAdaptMinDepth - 2;
+
+namespace {
+
+// one lane's polls of its sweep's running words
+struct AutoPoll {
+    hipStream_t st = nullptr;
+    const int* dwords = nullptr;  // device: ng running words
+    volatile int* ring = nullptr;  // pinned: kAutoRing x kGateWordsMax
+    hipEvent_t* ev = nullptr;
+    int ng = 0, queued = 0, seen = 0;
+    bool stopped = false;  // a finished poll read every word zero
+    void reset(hipStream_t s, int words) {
+        st = s;
+        ng = words;
+        queued = seen = 0;
+        stopped = false;
+    }
+    // fold in the finished polls; with `room` wait for the oldest while every ring slot is in flight
+    void observe(bool room) {
+        while (seen < queued && !stopped) {
+            const int slot = seen % kAutoRing;
+            if (room && queued - seen >= kAutoRing) {
+                KT_HIP(hipEventSynchronize(ev[slot]));
+            } else {
+                const hipError_t q = hipEventQuery(ev[slot]);
+                if (q == hipErrorNotReady) {
+                    (void)hipGetLastError();
+                    return;
+                }
+                KT_HIP(q);
+            }
+            int any = 0;
+            for (int k = 0; k < ng; ++k) any |= ring[slot * kGateWordsMax + k];
+            ++seen;
+            if (!any) stopped = true;
+        }
+    }
+    void queue() {
+        const int slot = queued % kAutoRing;
+        KT_HIP(hipMemcpyAsync(const_cast<int*>(ring) + slot * kGateWordsMax, dwords, sizeof(int) * ng,
+                              hipMemcpyDeviceToHost, st));
+        KT_HIP(hipEventRecord(ev[slot], st));
+        ++queued;
+    }
+};
+
+// a lane's device block: [state P x kAdaptState | guard snapshot P | running words]
+struct AutoDev {
+    double* state = nullptr;
+    double* gsnap = nullptr;
+    int* words = nullptr;
+    size_t bytes = 0;
+};
+
+AutoDev auto_dev(kt_context_s* ctx, int lane, int P) {
+    AutoDev d;
+    d.bytes = sizeof(double) * ((size_t)P * kAdaptState + P) + sizeof(int) * kGateWordsMax;
+    ctx->ws.auto_state[lane].ensure(d.bytes);
+    d.state = ctx->ws.auto_state[lane].as<double>();
+    d.gsnap = d.state + (size_t)P * kAdaptState;
+    d.words = reinterpret_cast<int*>(d.gsnap + P);
+    return d;
+}
+
+// zero state, every live column group's word non-zero (running)
+void auto_dev_reset(const AutoDev& d, int ng, hipStream_t st) {
+    KT_HIP(hipMemsetAsync(d.state, 0, d.bytes, st));
+    KT_HIP(hipMemsetAsync(d.words, 1, sizeof(int) * ng, st));
+}
+
+void auto_poll_bind(kt_context_s* ctx, int lane, AutoPoll& p) {
+    PinnedBuf& pw = ctx->ws.pin_auto;
+    pw.ensure(sizeof(int) * 4 * kAutoRing * kGateWordsMax);
+    p.ring = pw.as<int>() + (size_t)lane * kAutoRing * kGateWordsMax;
+    for (auto& e : ctx->ws.auto_ev[lane])
+        if (!e) KT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    p.ev = ctx->ws.auto_ev[lane];
+}
+
+// One sweep of `live` probes by the explicit CGS2 sweep on lane 0 with the
+// stopping test after every step, until its columns have all stopped or
+// reached m rows.  R (host): [record 3 m P | guard P | state | guard snapshot];
+// returns the record rows written.  Blocking.
+int explicit_auto_sweep(kt_matrix_s* A, const DevCSR& H, int P, int m, int fun, double rtol, uint64_t seed,
+                        int64_t base, int live, double* R) {
+    kt_context_s* ctx = A->ctx;
+    ExplicitSweep e(A, H, P, m, seed, base, nullptr, 0, 0, nullptr, R, nullptr, nullptr, 0, 0);
+    hipStream_t st = e.stream();
+    const int ng = (live + kWideCheckCols - 1) / kWideCheckCols;
+    const AutoDev d = auto_dev(ctx, 0, P);
+    AutoPoll poll;
+    auto_poll_bind(ctx, 0, poll);
+    poll.reset(st, ng);
+    poll.dwords = d.words;
+    auto_dev_reset(d, ng, st);
+    e.start();
+    int rows = 0;
+    for (int j = 0; j < m; ++j) {
+        poll.observe(false);
+        if (poll.stopped) break;
+        e.step(j);
+        rows = j + 1;
+        if (rows < kAutoFirstCheck) continue;
+        prof_begin(ctx, PROF_CHECK, st, P);
+        KT_HIP(launch_quad_check_wide(e.device_record(), m, P, rows, live, 0, nullptr, fun, rtol, d.state, d.words, st));
+        prof_end(ctx, PROF_CHECK, st);
+        if (rows % kAutoPoll == 0) {
+            poll.observe(true);
+            if (!poll.stopped) poll.queue();
+        }
+    }
+    e.finish(rows);
+    const size_t rec = (size_t)3 * m * P + P;
+    KT_HIP(hipMemcpyAsync(R + rec, d.state, sizeof(double) * ((size_t)P * kAdaptState + P), hipMemcpyDeviceToHost,
+                          st));
+    KT_HIP(hipStreamSynchronize(st));
+    return rows;
+}
+
+}  // namespace
+
+static void slq_trace_auto(kt_matrix_s* A, int fun, int m_max, double rtol, uint64_t seed, int64_t probe_offset,
+                           int64_t nprobes, int block, double* sum_q, double* sum_q2, double* q, int* depth,
+                           int64_t* capped) {
+    if (fun < KT_FUN_EXP || fun > KT_FUN_SQRT) fail(KT_ERR_ARG, "unknown fun code");
+    if (m_max > kAdaptMaxCap) fail(KT_ERR_ARG, "the Lanczos depth cap must be at most 256");
+    if (m_max <= 0) m_max = kAdaptDefaultCap;
+    if (!(rtol > 0.0)) rtol = kAdaptRtol;
+    if (nprobes < 0 || probe_offset < 0) fail(KT_ERR_ARG, "negative probe range");
+    if (block != 0 && !pow2_le128(block)) fail(KT_ERR_ARG, "block must be 0 or a power of two <= 128");
+    kt_context_s* ctx = A->ctx;
+    Workspace& w = ctx->ws;
+    if (w.slq_submitted != w.slq_collected)
+        fail(KT_ERR_ARG, "kt_slq_trace_auto: kt_slq_submit calls are outstanding on this context");
+    if (sum_q) *sum_q = 0.0;
+    if (sum_q2) *sum_q2 = 0.0;
+    if (capped) *capped = 0;
+    const int64_t n = A->n;
+    if (n == 0 || nprobes == 0) return;
+    const int m = m_max, P = block ? block : slq_auto_block(n, nprobes);
+    const int64_t nsw = (nprobes + P - 1) / P;
+    const int hy = std::min(m, kAutoHorizon);  // rows a y-form sweep may reach
+    // KT_SLQ_LANES=L (<= 4).  Default 4, where the fixed-depth y-form takes 2:
+    // a lane spends about a third of its time in its one-workgroup check, which
+    // only other lanes' passes can cover (the bench graph, 1,024 probes:
+    // 2.0 / 2.9 / 3.4 / 3.5 evaluations/s at 1 / 2 / 3 / 4 lanes)
+    const char* le = getenv("KT_SLQ_LANES");
+    const int lanes_env = le ? std::max(1, std::min(4, atoi(le))) : 4;
+    const int lanes = (int)std::max<int64_t>(1, std::min<int64_t>(nsw, lanes_env));
+    const char* ie = getenv("KT_SLQ_INT0");
+    const bool int0_env = !(ie && ie[0] == '0');
+    KT_HIP(hipSetDevice(ctx->device));
+    const DevCSR& H = hub_csr(A);
+    const bool int0 = int0_env && int0_applies(A->unit_values, H.max_row, hy);
+    // pinned, per sweep: [record 3 m P | guard P | state P x 8 | guard snapshot P]
+    const size_t rec = (size_t)3 * m * P + P, per = rec + (size_t)P * kAdaptState + P;
+    w.pin_auto_rec.ensure(sizeof(double) * per * nsw);
+    double* hrec = w.pin_auto_rec.as<double>();
+    std::vector<int> rows((size_t)nsw, 0);
+    auto live_of = [&](int64_t i) { return (int)std::min<int64_t>(P, nprobes - i * P); };
+    prof_recycle(ctx);
+    if (ctx->yform) {
+        struct Lane {
+            std::unique_ptr<YSweep> y;
+            AutoPoll poll;
+            AutoDev dev;
+            int64_t sweep = -1;
+            int j = 0;
+        };
+        std::vector<Lane> L(lanes);
+        int64_t next = 0;
+        for (int l = 0; l < lanes; ++l) {
+            if (l && !ctx->aux_stream[l - 1])
+                KT_HIP(hipStreamCreateWithFlags(&ctx->aux_stream[l - 1], hipStreamNonBlocking));
+            L[l].dev = auto_dev(ctx, l, P);
+            auto_poll_bind(ctx, l, L[l].poll);
+            L[l].poll.dwords = L[l].dev.words;
+        }
+        auto begin = [&](int l) {
+            Lane& s = L[l];
+            s.y.reset();
+            s.sweep = -1;
+            if (next >= nsw) return;
+            s.sweep = next++;
+            const int ng = (live_of(s.sweep) + kWideCheckCols - 1) / kWideCheckCols;
+            s.y.reset(new YSweep(A, H, P, m, seed, probe_offset + s.sweep * P, hrec + per * s.sweep, l, int0,
+                                 s.dev.words, ng));
+            s.poll.reset(s.y->stream(), ng);
+            auto_dev_reset(s.dev, ng, s.y->stream());
+            s.y->start();
+            s.j = 0;
+            rows[s.sweep] = 1;
+        };
+        auto end = [&](int l) {
+            Lane& s = L[l];
+            s.y->finish(rows[s.sweep]);
+            KT_HIP(hipMemcpyAsync(hrec + per * s.sweep + rec, s.dev.state,
+                                  sizeof(double) * ((size_t)P * kAdaptState + P), hipMemcpyDeviceToHost,
+                                  s.y->stream()));
+        };
+        for (int l = 0; l < lanes; ++l) begin(l);
+        // one launch group (step, check, poll) per lane in turn, so the lanes' work is queued side by side
+        for (bool any = true; any;) {
+            any = false;
+            for (int l = 0; l < lanes; ++l) {
+                Lane& s = L[l];
+                if (s.sweep < 0) continue;
+                any = true;
+                s.poll.observe(false);
+                if (s.poll.stopped || s.j + 1 >= hy) {
+                    end(l);
+                    begin(l);
+                    continue;
+                }
+                s.y->step(s.j);
+                const int d = s.j + 2;  // record rows complete after ordinary pass j
+                rows[s.sweep] = d;
+                ++s.j;
+                if (d < kAutoFirstCheck) continue;
+                hipStream_t st = s.y->stream();
+                prof_begin(ctx, PROF_CHECK, st, P);
+                KT_HIP(launch_quad_check_wide(s.y->device_record(), m, P, d, live_of(s.sweep), 0, nullptr, fun, rtol,
+                                              s.dev.state, s.dev.words, st, s.y->device_guard(), kYformGuard,
+                                              s.dev.gsnap));
+                prof_end(ctx, PROF_CHECK, st);
+                if (d % kAutoPoll == 0) {
+                    s.poll.observe(true);
+                    if (!s.poll.stopped) s.poll.queue();
+                }
+            }
+        }
+        KT_HIP(hipStreamSynchronize(ctx->stream));
+        for (int l = 1; l < lanes; ++l) KT_HIP(hipStreamSynchronize(ctx->aux_stream[l - 1]));
+    }
+    // sweeps for the explicit path: all of them without the y-form; else the
+    // guarded ones (counted as redone) and those still running at the horizon
+    int64_t redone = 0;
+    for (int64_t i = 0; i < nsw; ++i) {
+        double* R = hrec + per * i;
+        const int live = live_of(i);
+        bool hand = !ctx->yform;
+        if (ctx->yform) {
+            const double* st = R + rec;
+            const double* gs = st + (size_t)P * kAdaptState;
+            const double* g = R + (size_t)3 * m * P;
+            bool bad = false, running = false;
+            for (int c = 0; c < live; ++c) {
+                const bool stopped = st[(size_t)c * kAdaptState + 4] != 0.0;
+                bad |= !((stopped ? gs[c] : g[c]) >= kYformGuard);
+                running |= !stopped;
+            }
+            if (bad) ++redone;
+            hand = bad || (running && hy < m);
+        }
+        if (hand) rows[i] = explicit_auto_sweep(A, H, P, m, fun, rtol, seed, probe_offset + i * P, live, R);
+    }
+    ctx->yform_redone += redone;
+    // per probe on the host pool: its record truncated at its own depth
+    std::vector<double> qv((size_t)nprobes);
+    std::vector<int> dep((size_t)nprobes, 0);
+    std::vector<char> cap((size_t)nprobes, 0);
+    const int64_t chunk = 16;
+    HostPool::get().run((int)((nprobes + chunk - 1) / chunk), [&](int t) {
+        std::vector<double> al(m), off(m);
+        const int64_t pb = t * chunk, pe = std::min<int64_t>(nprobes, pb + chunk);
+        for (int64_t p = pb; p < pe; ++p) {
+            const int64_t i = p / P;
+            const int c = (int)(p % P);
+            const double* R = hrec + per * i;
+            const double* st = R + rec + (size_t)c * kAdaptState;
+            // a column the device did not stop ran every row its sweep wrote
+            const bool stopped = st[4] != 0.0;
+            const int d = stopped ? (int)st[3] : rows[i];
+            const int steps = record_tridiag_at(R, m, d, P, c, al.data(), off.data());
+            cap[p] = !stopped && !(R[(size_t)(2 * m + steps - 1) * P + c] < 1e-8);
+            dep[p] = steps;
+            qv[p] = (double)n * tridiag_quadrature(steps, al.data(), off.data(), fun);
+        }
+    }, 4);
+    double s1 = 0.0, s2 = 0.0;
+    int64_t ncap = 0;
+    int dmax = 0;
+    for (int64_t p = 0; p < nprobes; ++p) {
+        s1 += qv[p];
+        s2 += qv[p] * qv[p];
+        if (q) q[p] = qv[p];
+        if (depth) depth[p] = dep[p];
+        ncap += cap[p];
+        dmax = std::max(dmax, dep[p]);
+    }
+    if (sum_q) *sum_q = s1;
+    if (sum_q2) *sum_q2 = s2;
+    if (capped) *capped = ncap;
+    ctx->adapt_max_depth = std::max<int64_t>(ctx->adapt_max_depth, dmax);
+    ctx->adapt_capped += ncap;
+}
+
 }  // namespace kt
 
 #define KT_SLQ_TRY try {
@@ -1081,5 +1414,14 @@ extern "C" int kt_slq_collect(kt_matrix_t A, int ticket, double* sum_q, double* 
     KT_SLQ_TRY
     if (!A) fail(KT_ERR_ARG, "A is NULL");
     slq_collect(A, ticket, sum_q, sum_q2, q);
+    KT_SLQ_CATCH
+}
+
+extern "C" int kt_slq_trace_auto(kt_matrix_t A, int fun, int m_max, double rtol, uint64_t seed,
+                                 int64_t probe_offset, int64_t nprobes, int block, double* sum_q, double* sum_q2,
+                                 double* q, int* depth, int64_t* capped) {
+    KT_SLQ_TRY
+    if (!A) fail(KT_ERR_ARG, "A is NULL");
+    slq_trace_auto(A, fun, m_max, rtol, seed, probe_offset, nprobes, block, sum_q, sum_q2, q, depth, capped);
     KT_SLQ_CATCH
 }

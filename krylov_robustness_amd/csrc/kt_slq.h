@@ -78,13 +78,23 @@ inline bool int0_applies(bool unit_values, int64_t max_row, int m) {
 // behind the sign table, the first step (k_spmm_lanczos_first) gathers it and
 // the second reads it as Yold; from the third step on nothing differs, and
 // every record is bit-identical to the fp64 form's.
+// The resumable form (slq_trace_auto): constructed with gate != nullptr and m
+// the record's row capacity, every step(j) is the ordinary pass in its gated
+// form (never the half-gather last pass), so record row j + 1 is complete
+// after it and T_{j+2} can be tested; finish(rows) copies the rows written
+// and the guard.  int0 then needs int0_applies at the depth the sweep may
+// reach.  A fixed-depth sweep (gate == nullptr) queues what it always did.
 class YSweep {
    public:
     YSweep(kt_matrix_s* A, const DevCSR& M, int P, int m, uint64_t seed, int64_t probe_base, double* rec_host,
-           int lane, bool int0 = false);
+           int lane, bool int0 = false, const int* gate = nullptr, int ngate = 0);
     void start();
     void step(int j);
     void finish();
+    void finish(int rows);
+    const double* device_record() const { return trec; }
+    const double* device_guard() const { return guard; }
+    hipStream_t stream() const { return st; }
 
    private:
     double* rec_at(int row, int j) { return trec + (size_t)(row * m + j) * P; }
@@ -104,6 +114,8 @@ class YSweep {
     bool int0 = false;
     int16_t* T0 = nullptr;  // int0: y_0's row sums
     double s0 = 0.0;        // 1 / ||z||
+    const int* gate = nullptr;  // the resumable form: the sweep's running words
+    int ngate = 0;
 };
 
 // lanczos_sweep_y_block enqueued step by step: start(), step(j) for j < m - 1,

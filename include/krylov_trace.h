@@ -121,6 +121,36 @@ int kt_slq_trace_auto(kt_matrix_t A, int fun, int m_max, double rtol, uint64_t s
 /* The probes-per-sweep width kt_slq_trace picks when block == 0. */
 int kt_slq_plan(kt_matrix_t A, int64_t nprobes, int* block);
 
+/* Deflated stochastic estimator of diag f(A) (compute_centrality.m:9-10 is
+ * fun = KT_FUN_EXP: the subgraph centrality).  Q (n x kdef column-major,
+ * original row numbering, borrowed; NULL exactly when kdef == 0, 0 <= kdef <=
+ * 16) has orthonormal columns: max |Q'Q - I| > 1e-8 is KT_ERR_ARG.  With
+ * Pi = I - Q Q', F = f(A), G = F Q by m-step Lanczos and H = Q'G,
+ *   diag F = d0 + diag(Pi F Pi),  d0 = 2 rowsum(Q .* G) - rowsum((Q H) .* Q),
+ * for any orthonormal Q, and E[z .* (Pi F Pi z)] = diag(Pi F Pi) over
+ * Rademacher z.  For every probe p of [probe_offset, probe_offset + nprobes)
+ * (the stream of kt_slq_trace: splitmix64 keyed by the global probe index):
+ * z' = Pi z, the m-step Lanczos tridiagonal T of A from z'/||z'||,
+ * y = ||z'|| V f(T) e1, t_p = z .* (y - Q (Q'y)) and q_p = ||z'||^2 e1'f(T)e1.
+ *   dsum (n, required) = sum_p t_p        dsum2 (n) = sum_p t_p .* t_p
+ *   sum_q = sum_p q_p                     sum_q2 = sum_p q_p^2
+ *   d0 (n; zeros when kdef == 0)
+ * dsum2, d0, sum_q, sum_q2 are optional.  The estimate is d0 + dsum / N, row
+ * i's standard error sqrt((dsum2_i / N - (dsum_i / N)^2) / (N - 1)); in exact
+ * arithmetic sum_i dsum_i = sum_q.  All outputs but d0 are plain sums over the
+ * probe range: shards of a range add.  block = probes per sweep, a power of
+ * two from 1 to 16 (0: 16); nprobes >= 1; 1 <= m <= 256; fun unscaled, as in
+ * kt_slq_trace.  Probe p's terms depend only on (A, fun, m, seed, p, block,
+ * Q), dsum and dsum2 only on those and the range -- not on the lane count,
+ * timing or other calls; the sums are accumulated in sweep order without
+ * atomics, so two identical calls return identical bits.  Each sweep in
+ * flight keeps its Lanczos basis (m n block doubles): KT_ERR_ALLOC if not
+ * even one fits.  Blocking; refused while kt_slq_submit tickets are
+ * outstanding. */
+int kt_diag_fun(kt_matrix_t A, int fun, int m, uint64_t seed, int64_t probe_offset, int64_t nprobes, int block,
+                int64_t kdef, const double* Q, double* dsum, double* dsum2, double* d0, double* sum_q,
+                double* sum_q2);
+
 /* ---- block-Krylov entry points (bs = number of columns of U, <= 128) ------
  * U: n x rk column-major in ORIGINAL row numbering; B: rk x rk column-major.
  * it <= 0 selects the reference default min(100, n). */
@@ -374,7 +404,10 @@ int kt_eigs_leading(kt_matrix_t A, double tol, int maxit, double* lambda, double
  * by a given block (k_spmm_lanczos in mc_trace's quadrature-only columns),
  * 4 = the expmv Taylor-term kernel (k_expmv_rows / k_expmv_step, one launch
  * per term; a term queued past its stage's stop is a short no-op launch),
- * 6 = the stopping test of kt_slq_trace_auto's sweeps (k_quad_check_wide).
+ * 6 = the stopping test of kt_slq_trace_auto's sweeps (k_quad_check_wide),
+ * 7 = kt_diag_fun's combine and accumulate kernels (k_diag_combine,
+ * k_diag_finish), 8 = its start-block kernels (k_diag_qtz, k_diag_start; its
+ * sweeps' passes report in 3, or 0 and 1 for a sweep redone explicitly).
  * Returns launch count and summed milliseconds. */
 int kt_profile_enable(kt_context_t ctx, int enable);
 int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* total_ms);

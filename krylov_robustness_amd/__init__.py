@@ -8,7 +8,7 @@ include/krylov_trace.h); this package is the Python mirror of the reference
 interface used by tests and bench.py.
 """
 from ._lib import KrylovError, KrylovLibraryError, FUN_CODES, LIB_PATH
-from .core import (Context, DeviceMatrix, default_context, device_count, expmv,
+from .core import (Context, DeviceMatrix, DiagEstimate, default_context, device_count, diag_fun, expmv,
                    eigs_leading, frechet_entries, function_multiple_entries, hessianfcn, hessianfcn_exp,
                    hessianfcn_fun, householder_qr,
                    fun_and_grad_krylov_exp, fun_and_grad_krylov_fun, fun_update, lanczos_fmv, lanczos_fmv_auto,
@@ -25,7 +25,7 @@ from .datasets import load_problem, load_unweighted, prepare_unweighted, prepare
 __all__ = [
     "KrylovError", "KrylovLibraryError", "FUN_CODES", "LIB_PATH", "Context", "DeviceMatrix",
     "default_context", "device_count", "slq_plan", "slq_quadforms", "slq_submit", "slq_collect", "slq_trace", "slq_quadforms_auto",
-    "slq_trace_auto", "normest",
+    "slq_trace_auto", "normest", "diag_fun", "DiagEstimate",
     "trace_fun_update", "fun_update", "fun_and_grad_krylov_exp", "fun_and_grad_krylov_fun",
     "mc_trace", "trace_exp", "expmv", "lanczos_fmv", "lanczos_fmv_auto", "trace_fun_update_pairs", "krylov_miobi",
     "greedy_krylov", "find_top_edges", "find_top_missing_edges", "compute_centrality",

@@ -290,6 +290,67 @@ def slq_trace_auto(A, nprobes: int, m_max: int = 128, rtol=None, seed: int = 0, 
     return s1 / max(nprobes, 1), q
 
 
+class DiagEstimate:
+    """Result of diag_fun: the sums kt_diag_fun returns over the probe range
+    (dsum, dsum2, sum_q, sum_q2 add across shards of a range; d0 is the
+    deflated part) and the estimate they give, mean = d0 + dsum / nprobes,
+    with its per-node standard error."""
+
+    __slots__ = ("d0", "dsum", "dsum2", "sum_q", "sum_q2", "nprobes")
+
+    def __init__(self, d0, dsum, dsum2, sum_q, sum_q2, nprobes):
+        self.d0, self.dsum, self.dsum2 = d0, dsum, dsum2
+        self.sum_q, self.sum_q2, self.nprobes = float(sum_q), float(sum_q2), int(nprobes)
+
+    @property
+    def mean(self):
+        return self.d0 + self.dsum / self.nprobes
+
+    @property
+    def stderr(self):
+        N = self.nprobes
+        if N < 2:
+            return np.full_like(self.dsum, np.inf)
+        var = np.maximum(self.dsum2 / N - (self.dsum / N) ** 2, 0.0)
+        return np.sqrt(var / (N - 1))
+
+
+def diag_fun(A, nprobes: int, m: int = 30, seed: int = 0, fun="exp", probe_offset: int = 0, block: int = 0,
+             deflate=None, ctx: Optional[Context] = None):
+    """Deflated stochastic estimate of diag f(A) (kt_diag_fun; f = exp is the
+    subgraph centrality of compute_centrality.m:9-10) from the Rademacher
+    probes [probe_offset, probe_offset + nprobes) of slq_quadforms' stream.
+    deflate: None, an n x k array with orthonormal columns (k <= 16; any
+    orthonormal Q keeps the estimator unbiased), or 1 = the unit leading
+    eigenvector from eigs_leading.  Returns a DiagEstimate."""
+    if isinstance(deflate, (int, np.integer)) and not isinstance(deflate, bool):
+        if int(deflate) not in (0, 1):
+            raise ValueError("diag_fun: deflate as an int supports only 1 (the leading eigenvector); "
+                             "pass an orthonormal n x k array for more")
+        deflate = int(deflate) or None
+    D = _dev(A, ctx)
+    n, _ = D.info()
+    nprobes = int(nprobes)
+    Q = None
+    if deflate is not None:
+        if isinstance(deflate, int):
+            Q = _colmajor(eigs_leading(D, ctx=ctx)[1])
+        else:
+            Q = _colmajor(deflate)
+        if Q.shape[0] != n:
+            raise ValueError(f"diag_fun: deflate has {Q.shape[0]} rows, the matrix {n}")
+    k = 0 if Q is None else Q.shape[1]
+    dsum = np.zeros(max(n, 1))
+    dsum2 = np.zeros(max(n, 1))
+    d0 = np.zeros(max(n, 1))
+    s1 = C.c_double()
+    s2 = C.c_double()
+    _lib.check(_lib.load().kt_diag_fun(
+        D.handle, _fun_code(fun), int(m), int(seed) & 0xFFFFFFFFFFFFFFFF, int(probe_offset), nprobes, int(block),
+        k, _dptr(Q) if k else None, _dptr(dsum), _dptr(dsum2), _dptr(d0), C.byref(s1), C.byref(s2)))
+    return DiagEstimate(d0[:n], dsum[:n], dsum2[:n], s1.value, s2.value, nprobes)
+
+
 # ---------------------------------------------------------------------------
 # block-Krylov entry points (reference names and argument order)
 # ---------------------------------------------------------------------------

@@ -135,10 +135,12 @@ struct ProfSlot {
 
 // PROF_FIRST: the compact sweep's first step (k_spmm_lanczos_first) alone; the
 // launch is also one of the sweep's step passes in PROF_SPMM.  PROF_CHECK:
-// the stopping test of an error-controlled SLQ sweep (k_quad_check_wide)
+// the stopping test of an error-controlled SLQ sweep (k_quad_check_wide).
+// PROF_DIAG / PROF_DIAG_START: kt_diag_fun's combine + accumulate kernels and
+// its start-block kernels (kt_diag.hip)
 enum {
     PROF_SPMM = 0, PROF_UPDATE = 1, PROF_START = 2, PROF_YBLOCK = 3, PROF_EXPMV = 4, PROF_FIRST = 5,
-    PROF_CHECK = 6, PROF_NSLOTS = 7
+    PROF_CHECK = 6, PROF_DIAG = 7, PROF_DIAG_START = 8, PROF_NSLOTS = 9
 };
 
 // Buffers of one probe-sweep lane (kt_slq.cpp); two lanes let two sweeps

@@ -186,6 +186,32 @@ hipError_t launch_perm_rows(int n, int cols, const int* perm, int gather, const 
                             double* dst, int ldd, hipStream_t st);
 hipError_t launch_axpby(int n, int nc, double a, const double* X, int ldx, double b, double* Y,
                         int ldy, hipStream_t st);
+// diag f(A) estimator (kt_diag.hip; driver kt_diag_fun.cpp).  Blocks are n x P
+// row-major in the probe sweep's row order, P a power of two <= 16; Q is the
+// deflation block, n x KP row-major, KP in {0, 1, 4, 16} (0: none).  The
+// reducing kernels write `grid` workgroup partials of K values each
+// (K = KP P, or P for the norms); launch_diag_sum_parts adds them in order.
+int diag_grid(int n, int P);
+hipError_t launch_diag_qtz(int P, int KP, int grid, int n, uint64_t seed, int64_t base, int nc, const int* perm,
+                           const double* Q, double* part, hipStream_t st);
+hipError_t launch_diag_sum_parts(int nparts, int K, const double* part, double* out, hipStream_t st);
+// X = z - Q c (c: KP x P), columns >= nc zero; part: the columns' squared-norm partials
+hipError_t launch_diag_start(int P, int KP, int grid, int n, uint64_t seed, int64_t base, int nc, const int* perm,
+                             const double* Q, const double* c, double* X, double* part, hipStream_t st);
+// y = sum_{j < depth[p]} W[j, p] V_j (slot j at V + j sstride; mdepth = max depth).
+// KP = 0: dsum[perm[r]] += sum_p z y, dsum2 likewise with squares.  KP > 0: y
+// into Y and the partials of Q' y into part.
+hipError_t launch_diag_combine(int P, int KP, int grid, int n, int m, int mdepth, const double* V, int64_t sstride,
+                               const double* W, const int* depth, uint64_t seed, int64_t base, const int* perm,
+                               const double* Q, double* Y, double* part, double* dsum, double* dsum2,
+                               hipStream_t st);
+// t = z .* (Y - Q c) reduced over the row's probes into dsum / dsum2
+hipError_t launch_diag_finish(int P, int KP, int grid, int n, uint64_t seed, int64_t base, const int* perm,
+                              const double* Q, const double* c, const double* Y, double* dsum, double* dsum2,
+                              hipStream_t st);
+// d0 = 2 rowsum(Q .* G) - rowsum((Q H) .* Q); Q, G n x ld row-major, H k x k column-major
+hipError_t launch_diag_d0(int n, int k, const double* Q, const double* G, int ld, const double* H, double* d0,
+                          hipStream_t st);
 int inf_norm_blocks();
 // normest1 (t = 1) reductions, normest1_blocks(n) partials each: sum |Y| in
 // partial[0, nb), S_prev . S in partial[nb, 2 nb), S = mysign(Y); per-block

@@ -373,12 +373,6 @@ void lanczos_sweep_y_block(kt_matrix_s* A, const DevCSR& M, int P, int m, const 
     s.finish();
 }
 
-// A y-form probe is accepted when every used beta_k^2 kept at least this
-// fraction of ||y_{k-1}||^2 (its Gram-identity cancellation then costs at most
-// ~1e4 ulp); otherwise its sweep is recomputed by the explicit CGS2 sweep.
-// Measured minimum on the golden graphs and Chung-Lu up to m = 100: 6.4e-3.
-constexpr double kYformGuard = 1e-4;
-
 // Column c of a sweep record -> symmetric tridiagonal (alpha, off); returns
 // the number of steps before a lucky breakdown (lanczos_krylov.m:91-93).
 int record_tridiag(const double* R, int m, int P, int c, double* al, double* off) {

@@ -258,20 +258,30 @@ def edge2low_rank(E, n, value=-1.0):
     return U, B
 
 
-def compute_centrality(A, kind="eig", ctx: Optional[Context] = None):
+def compute_centrality(A, kind="eig", ctx: Optional[Context] = None, **kw):
     """compute_centrality.m: 'eig' = abs(leading eigenvector) (:15-17), on the
     device when A is a DeviceMatrix (kt_eigs_leading), else scipy eigsh;
-    'deg' = column sums (:18-19)."""
+    'deg' = column sums (:18-19); 'exp' = diag(expm(A)), the subgraph
+    centrality (:9-10): the dense expm for a host matrix, as the reference,
+    and for a DeviceMatrix the deflated stochastic estimate diag_fun(A,
+    nprobes=256, deflate=1).mean (kw: nprobes, deflate, m, seed, block)."""
     import scipy.sparse as sp
     import scipy.sparse.linalg as sla
     if isinstance(A, DeviceMatrix):
         if kind == "deg":
             return np.asarray(A.to_scipy().sum(axis=0)).ravel()
+        if kind == "exp":
+            from .core import diag_fun
+            return diag_fun(A, kw.get("nprobes", 256), m=kw.get("m", 30), seed=kw.get("seed", 0),
+                            block=kw.get("block", 0), deflate=kw.get("deflate", 1), ctx=ctx).mean
         from .core import eigs_leading
         return np.abs(eigs_leading(A, ctx=ctx)[1])
     A = sp.csr_matrix(A, dtype=np.float64)
     if kind == "deg":
         return np.asarray(A.sum(axis=0)).ravel()
+    if kind == "exp":
+        import scipy.linalg as sl
+        return np.diag(sl.expm(A.toarray())).copy()
     _, u = sla.eigsh(A, k=1, which="LM")  # eigs(A, 1): largest magnitude
     return np.abs(u[:, 0])
 

@@ -322,7 +322,8 @@ struct kt_matrix_s {
     bool unit_values = false;  // every stored value == 1.0 (unweighted adjacency)
     int symmetric = -1;        // -1 unknown, 0 no, 1 yes (checked on the host copy)
     // hub: rows relabelled by descending degree class (hubs first) and, inside
-    // a class, clustered by a shared neighbour (kt_order.h) for the probe
+    // a class, clustered by a shared neighbour with same-class neighbours
+    // chained into runs of adjacent rows (kt_order.h chain_order) for the probe
     // hot path; probes stay keyed by ORIGINAL index via hub.perm, so results
     // do not depend on the relabelling.
     kt::DevCSR hub;

@@ -351,8 +351,9 @@ void refresh_device(kt_matrix_s* A) {
 const DevCSR& hub_csr(kt_matrix_s* A) {
     if (A->hub.built) return A->hub;
     const int64_t n = A->n;
-    // hubs first, neighbour-clustered inside a degree class (kt_order.h)
-    hub_order(n, A->h_rowptr.data(), A->h_col.data(), A->long_thresh, A->new2old);
+    // hubs first, neighbour-clustered inside a degree class, same-class
+    // neighbours chained (kt_order.h)
+    chain_order(n, A->h_rowptr.data(), A->h_col.data(), A->long_thresh, A->new2old);
     A->old2new.resize(n);
     for (int64_t r = 0; r < n; ++r) A->old2new[A->new2old[r]] = (int32_t)r;
     build_csr(A, A->new2old, A->hub);

@@ -126,3 +126,74 @@ def relabel_primary_quad(A, orig):
 
 def relabel_primary_exact(A, orig):
     return _relabel_primary(A, orig, exact=True)
+
+
+def _relabel_chain(A, orig, cap=0, long_thresh=64):
+    """csrc/kt_order.h chain_order on top of relabel_primary_quad: the base
+    order is walked and from each row not yet placed a run starts -- the row,
+    then its not yet placed same-class neighbour of smallest degree rank (in
+    the hubs-first labels of A the rank IS the label, and sorted indices list
+    a row's neighbours by rank), and so on from that one until none is left
+    (or the run holds `cap` rows, 0 = no cap).  Rows above long_thresh are not
+    chained."""
+    n = A.shape[0]
+    indptr, indices = A.indptr, A.indices
+    deg = np.diff(indptr)
+    cls = np.where(deg > long_thresh, -1, (deg + 3) // 4)  # -1: never eligible
+    # per row: its same-class neighbours, ascending label, self loops dropped
+    rows = np.repeat(np.arange(n), deg)
+    keep = (cls[rows] == cls[indices]) & (cls[rows] >= 0) & (rows != indices)
+    cptr = np.concatenate([[0], np.cumsum(np.bincount(rows[keep], minlength=n))]).tolist()
+    cand = indices[keep].tolist()
+    placed = bytearray(n)
+    out = []
+    for start in relabel_primary_quad(A, orig).tolist():
+        if placed[start]:
+            continue
+        cur, length = start, 0
+        while cur >= 0:
+            placed[cur] = 1
+            out.append(cur)
+            length += 1
+            nxt = -1
+            if not cap or length < cap:
+                for k in range(cptr[cur], cptr[cur + 1]):
+                    if not placed[cand[k]]:
+                        nxt = cand[k]
+                        break
+            cur = nxt
+    return np.asarray(out, dtype=np.int64)
+
+
+def relabel_chain(A, orig):
+    return _relabel_chain(A, orig)
+
+
+def relabel_chain_pairs(A, orig):
+    return _relabel_chain(A, orig, cap=2)
+
+
+def relabel_chain_cap8(A, orig):
+    return _relabel_chain(A, orig, cap=8)
+
+
+def contiguous_chunks(A, P=16, long_thresh=64, chunk=64):
+    """Schedule for the relabelled graphs above: each XCD walks one contiguous
+    slice of the short rows, cut at 64-row chunk boundaries into eight slices
+    of equal weight (a row weighs its nonzeros plus 3, the model's lines per
+    row); the long rows lead the order and are dealt as in run.py's baseline."""
+    n = A.shape[0]
+    deg = np.diff(A.indptr)
+    n_long = int((deg > long_thresh).sum())
+    assert np.all(deg[:n_long] > long_thresh)
+    lists = [list(range(x, n_long, 8)) for x in range(8)]
+    w = np.cumsum(deg[n_long:] + 3)
+    nchunks = -(-(n - n_long) // chunk)
+    cw = w[np.minimum(np.arange(1, nchunks + 1) * chunk, n - n_long) - 1] if nchunks else np.zeros(0)
+    cuts = [0] + [int(np.searchsorted(cw, cw[-1] * x / 8)) for x in range(1, 8)] + [nchunks]
+    for x in range(8):
+        lists[x] = np.concatenate([np.asarray(lists[x], dtype=np.int64),
+                                   np.arange(n_long + cuts[x] * chunk, min(n_long + cuts[x + 1] * chunk, n))])
+    order = np.concatenate(lists)
+    xoff = np.concatenate([[0], np.cumsum([len(l) for l in lists])])
+    return order, xoff

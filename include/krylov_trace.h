@@ -151,6 +151,31 @@ int kt_diag_fun(kt_matrix_t A, int fun, int m, uint64_t seed, int64_t probe_offs
                 int64_t kdef, const double* Q, double* dsum, double* dsum2, double* d0, double* sum_q,
                 double* sum_q2);
 
+/* The same estimator for entries of f(A) on a pair list.  fun, m, seed,
+ * probe_offset, nprobes, block, kdef, Q, sum_q and sum_q2 are kt_diag_fun's,
+ * with its checks, probe stream, padded deflation widths and sweep lanes.
+ * Pairs e = (ei[e], ej[e]) are 0-based in original row numbering; i == j,
+ * repeated pairs and both orientations are allowed, and every pair owns its
+ * output slot.  npairs < 1, an index outside [0, n) or a NULL ei, ej or esum
+ * is KT_ERR_ARG.  With yt_p = y - Q (Q'y) of probe p (kt_diag_fun's vector),
+ *   t_p[e] = (z_i yt_p[j] + z_j yt_p[i]) / 2,     E[t_p[e]] = (Pi F Pi)_ij
+ *   esum (npairs, required) = sum_p t_p    esum2 (npairs) = sum_p t_p .* t_p
+ *   e0[e] = sum_c (Q_ic G_jc + G_ic Q_jc)
+ *           - (sum_c (QH)_ic Q_jc + (QH)_jc Q_ic) / 2     (zeros when kdef == 0)
+ * since F = Pi F Pi + Q G' + G Q' - Q H Q' for any orthonormal Q.  esum2 and
+ * e0 are optional.  The estimate is e0 + esum / N with kt_diag_fun's standard
+ * error; for i == j the terms are kt_diag_fun's own.  All outputs but e0 are
+ * plain sums over the probe range: shards add.  A probe's terms depend only
+ * on (A, fun, m, seed, p, block, Q) and the pair, esum and esum2 only on those
+ * and the range -- not on the lane count, timing or other calls; the sums are
+ * accumulated in sweep order without atomics, so two identical calls, and a
+ * call on one lane, return identical bits.  KT_ERR_ALLOC if not even one
+ * sweep's basis fits.  Blocking; refused while kt_slq_submit tickets are
+ * outstanding. */
+int kt_entries_fun(kt_matrix_t A, int fun, int m, uint64_t seed, int64_t probe_offset, int64_t nprobes, int block,
+                   int64_t kdef, const double* Q, int64_t npairs, const int64_t* ei, const int64_t* ej,
+                   double* esum, double* esum2, double* e0, double* sum_q, double* sum_q2);
+
 /* ---- block-Krylov entry points (bs = number of columns of U, <= 128) ------
  * U: n x rk column-major in ORIGINAL row numbering; B: rk x rk column-major.
  * it <= 0 selects the reference default min(100, n). */
@@ -407,7 +432,9 @@ int kt_eigs_leading(kt_matrix_t A, double tol, int maxit, double* lambda, double
  * 6 = the stopping test of kt_slq_trace_auto's sweeps (k_quad_check_wide),
  * 7 = kt_diag_fun's combine and accumulate kernels (k_diag_combine,
  * k_diag_finish), 8 = its start-block kernels (k_diag_qtz, k_diag_start; its
- * sweeps' passes report in 3, or 0 and 1 for a sweep redone explicitly).
+ * sweeps' passes report in 3, or 0 and 1 for a sweep redone explicitly),
+ * 9 = kt_entries_fun's pair kernels (k_entries_accumulate, k_entries_e0; its
+ * sweeps, start blocks and combine report in 3, 8 and 7 as kt_diag_fun's do).
  * Returns launch count and summed milliseconds. */
 int kt_profile_enable(kt_context_t ctx, int enable);
 int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* total_ms);

@@ -8,7 +8,8 @@ include/krylov_trace.h); this package is the Python mirror of the reference
 interface used by tests and bench.py.
 """
 from ._lib import KrylovError, KrylovLibraryError, FUN_CODES, LIB_PATH
-from .core import (Context, DeviceMatrix, DiagEstimate, default_context, device_count, diag_fun, expmv,
+from .core import (Context, DeviceMatrix, DiagEstimate, EntryEstimate, default_context, device_count, diag_fun,
+                   entries_fun, expmv,
                    eigs_leading, frechet_entries, function_multiple_entries, hessianfcn, hessianfcn_exp,
                    hessianfcn_fun, householder_qr,
                    fun_and_grad_krylov_exp, fun_and_grad_krylov_fun, fun_update, lanczos_fmv, lanczos_fmv_auto,
@@ -16,7 +17,7 @@ from .core import (Context, DeviceMatrix, DiagEstimate, default_context, device_
                    slq_trace_auto, trace_exp,
                    trace_fun_update)
 from .greedy import (compute_centrality, default_greedy_tol, edge2low_rank, find_top_edges,
-                     find_top_missing_edges, greedy_krylov, krylov_miobi, krylov_miobi_sharded,
+                     find_top_edges_fun, find_top_missing_edges, greedy_krylov, krylov_miobi, krylov_miobi_sharded,
                      miobi_loop, select_extreme, trace_fun_update_pairs)
 from . import datasets, matv73
 from .dist import mc_trace_sharded, trace_exp_sharded
@@ -25,7 +26,7 @@ from .datasets import load_problem, load_unweighted, prepare_unweighted, prepare
 __all__ = [
     "KrylovError", "KrylovLibraryError", "FUN_CODES", "LIB_PATH", "Context", "DeviceMatrix",
     "default_context", "device_count", "slq_plan", "slq_quadforms", "slq_submit", "slq_collect", "slq_trace", "slq_quadforms_auto",
-    "slq_trace_auto", "normest", "diag_fun", "DiagEstimate",
+    "slq_trace_auto", "normest", "diag_fun", "DiagEstimate", "entries_fun", "EntryEstimate", "find_top_edges_fun",
     "trace_fun_update", "fun_update", "fun_and_grad_krylov_exp", "fun_and_grad_krylov_fun",
     "mc_trace", "trace_exp", "expmv", "lanczos_fmv", "lanczos_fmv_auto", "trace_fun_update_pairs", "krylov_miobi",
     "greedy_krylov", "find_top_edges", "find_top_missing_edges", "compute_centrality",

@@ -68,6 +68,8 @@ SIGNATURES = [
     ("kt_slq_plan", C.c_int, [_mat_p, C.c_int64, _ip]),
     ("kt_diag_fun", C.c_int, [_mat_p, C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int64,
                               _dp, _dp, _dp, _dp, _dp, _dp]),
+    ("kt_entries_fun", C.c_int, [_mat_p, C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_int64, C.c_int, C.c_int64,
+                                 _dp, C.c_int64, _i64p, _i64p, _dp, _dp, _dp, _dp, _dp]),
     ("kt_normest", C.c_int, [_mat_p, C.c_double, _dp]),
     ("kt_trace_fun_update", C.c_int, [_mat_p, C.c_int64, _dp, _dp, C.c_double, C.c_int, C.c_int,
                                       _dp, _ip, _ip]),

@@ -323,22 +323,11 @@ def diag_fun(A, nprobes: int, m: int = 30, seed: int = 0, fun="exp", probe_offse
     deflate: None, an n x k array with orthonormal columns (k <= 16; any
     orthonormal Q keeps the estimator unbiased), or 1 = the unit leading
     eigenvector from eigs_leading.  Returns a DiagEstimate."""
-    if isinstance(deflate, (int, np.integer)) and not isinstance(deflate, bool):
-        if int(deflate) not in (0, 1):
-            raise ValueError("diag_fun: deflate as an int supports only 1 (the leading eigenvector); "
-                             "pass an orthonormal n x k array for more")
-        deflate = int(deflate) or None
+    deflate = _deflate_arg("diag_fun", deflate)
     D = _dev(A, ctx)
     n, _ = D.info()
     nprobes = int(nprobes)
-    Q = None
-    if deflate is not None:
-        if isinstance(deflate, int):
-            Q = _colmajor(eigs_leading(D, ctx=ctx)[1])
-        else:
-            Q = _colmajor(deflate)
-        if Q.shape[0] != n:
-            raise ValueError(f"diag_fun: deflate has {Q.shape[0]} rows, the matrix {n}")
+    Q = _deflation("diag_fun", D, n, deflate, ctx)
     k = 0 if Q is None else Q.shape[1]
     dsum = np.zeros(max(n, 1))
     dsum2 = np.zeros(max(n, 1))
@@ -349,6 +338,90 @@ def diag_fun(A, nprobes: int, m: int = 30, seed: int = 0, fun="exp", probe_offse
         D.handle, _fun_code(fun), int(m), int(seed) & 0xFFFFFFFFFFFFFFFF, int(probe_offset), nprobes, int(block),
         k, _dptr(Q) if k else None, _dptr(dsum), _dptr(dsum2), _dptr(d0), C.byref(s1), C.byref(s2)))
     return DiagEstimate(d0[:n], dsum[:n], dsum2[:n], s1.value, s2.value, nprobes)
+
+
+class EntryEstimate:
+    """Result of entries_fun: the sums kt_entries_fun returns over the probe
+    range, one slot per pair (esum, esum2, sum_q, sum_q2 add across shards of
+    a range; e0 is the deflated part), and the estimate they give, mean = e0 +
+    esum / nprobes, with its per-pair standard error."""
+
+    __slots__ = ("e0", "esum", "esum2", "sum_q", "sum_q2", "nprobes")
+
+    def __init__(self, e0, esum, esum2, sum_q, sum_q2, nprobes):
+        self.e0, self.esum, self.esum2 = e0, esum, esum2
+        self.sum_q, self.sum_q2, self.nprobes = float(sum_q), float(sum_q2), int(nprobes)
+
+    @property
+    def mean(self):
+        return self.e0 + self.esum / self.nprobes
+
+    @property
+    def stderr(self):
+        N = self.nprobes
+        if N < 2:
+            return np.full_like(self.esum, np.inf)
+        var = np.maximum(self.esum2 / N - (self.esum / N) ** 2, 0.0)
+        return np.sqrt(var / (N - 1))
+
+
+def _deflate_arg(who, deflate):
+    """deflate of diag_fun / entries_fun checked before a device is touched:
+    None, 1 (the leading eigenvector) or the array."""
+    if isinstance(deflate, (int, np.integer)) and not isinstance(deflate, bool):
+        if int(deflate) not in (0, 1):
+            raise ValueError(f"{who}: deflate as an int supports only 1 (the leading eigenvector); "
+                             "pass an orthonormal n x k array for more")
+        deflate = int(deflate) or None
+    return deflate
+
+
+def _deflation(who, D, n, deflate, ctx):
+    """... and as a column-major n x k block (or None)."""
+    if deflate is None:
+        return None
+    Q = _colmajor(eigs_leading(D, ctx=ctx)[1]) if isinstance(deflate, int) else _colmajor(deflate)
+    if Q.shape[0] != n:
+        raise ValueError(f"{who}: deflate has {Q.shape[0]} rows, the matrix {n}")
+    return Q
+
+
+def entries_fun(A, pairs, nprobes: int, m: int = 30, seed: int = 0, fun="exp", probe_offset: int = 0,
+                block: int = 0, deflate=None, ctx: Optional[Context] = None):
+    """Deflated stochastic estimate of the entries f(A)[i, j] on a pair list
+    (kt_entries_fun), from the probes and sweeps of diag_fun: one sweep set
+    for any number of pairs.  pairs: (npairs, 2) integers, 0-BASED; i == j,
+    repeats and both orientations are allowed, each row has its own slot.
+    nprobes, m, seed, fun, probe_offset, block and deflate are diag_fun's.
+    Returns an EntryEstimate."""
+    P = np.asarray(pairs)
+    if P.ndim != 2 or P.shape[1] != 2 or P.shape[0] < 1:
+        raise ValueError(f"entries_fun: pairs must have shape (npairs >= 1, 2), got {P.shape}")
+    if not np.issubdtype(P.dtype, np.integer):
+        raise ValueError(f"entries_fun: pairs must be integers, got {P.dtype}")
+    n = A.n if isinstance(A, DeviceMatrix) else np.shape(A)[0]
+    if P.min() < 0 or P.max() >= n:
+        raise ValueError(f"entries_fun: pair indices must lie in [0, {n}) (0-based)")
+    deflate = _deflate_arg("entries_fun", deflate)
+    D = _dev(A, ctx)
+    n, _ = D.info()
+    Q = _deflation("entries_fun", D, n, deflate, ctx)
+    k = 0 if Q is None else Q.shape[1]
+    nprobes = int(nprobes)
+    npairs = P.shape[0]
+    ei = np.ascontiguousarray(P[:, 0], dtype=np.int64)
+    ej = np.ascontiguousarray(P[:, 1], dtype=np.int64)
+    esum = np.zeros(npairs)
+    esum2 = np.zeros(npairs)
+    e0 = np.zeros(npairs)
+    s1 = C.c_double()
+    s2 = C.c_double()
+    i64p = C.POINTER(C.c_int64)
+    _lib.check(_lib.load().kt_entries_fun(
+        D.handle, _fun_code(fun), int(m), int(seed) & 0xFFFFFFFFFFFFFFFF, int(probe_offset), nprobes, int(block),
+        k, _dptr(Q) if k else None, npairs, ei.ctypes.data_as(i64p), ej.ctypes.data_as(i64p), _dptr(esum),
+        _dptr(esum2), _dptr(e0), C.byref(s1), C.byref(s2)))
+    return EntryEstimate(e0, esum, esum2, s1.value, s2.value, nprobes)
 
 
 # ---------------------------------------------------------------------------

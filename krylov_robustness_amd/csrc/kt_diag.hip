@@ -1,5 +1,6 @@
 // kt_diag.hip -- streaming kernels of the deflated stochastic estimator of
-// diag f(A) (kt_diag_fun.cpp).
+// diag f(A) (kt_diag_fun.cpp) and of its off-diagonal twin on
+// a pair list (kt_entries_fun, §4.2c: k_entries_accumulate, k_entries_e0).
 //
 // Every kernel walks an n x P row-major block (P probes of one sweep, rows in
 // the hubs-first order of the probe sweep) with LPR = max(P / 2, 1) lanes per
@@ -221,9 +222,10 @@ template <int P> __device__ __forceinline__ double row_sum(const double* t) {
 // other half of a 16-byte pair and never enter a sum, slots at or past mdepth
 // (the largest cut) are not read.  KP = 0: t = z .* y is reduced over the
 // row's probes and added to dsum / dsum2 (y is never stored).  KP > 0: y goes
-// to Y and the partials of Q' y to part.
+// to Y and the partials of Q' y to part.  YONLY (KP = 0, kt_entries_fun): y
+// goes to Y and nothing else is formed.
 // LDS (dynamic): W (m x P), then the 4 * KP * P reduction scratch.
-template <int P, int KP>
+template <int P, int KP, bool YONLY = false>
 __global__ __launch_bounds__(kDiagBlock) void k_diag_combine(int n, int m, int mdepth, const double* __restrict__ V,
                                                              int64_t sstride, const double* __restrict__ W,
                                                              const int* __restrict__ depth, uint64_t seed,
@@ -272,7 +274,9 @@ __global__ __launch_bounds__(kDiagBlock) void k_diag_combine(int n, int m, int m
                     }
             }
         }
-        if constexpr (KP == 0) {
+        if constexpr (YONLY) {
+            if (live) st_vec<G::VEC>(Y + r * P + sub * G::VEC, y);
+        } else if constexpr (KP == 0) {
             double t[G::VEC], t2[G::VEC];
             const uint64_t i = live ? (perm ? (uint64_t)perm[r] : (uint64_t)r) : 0;
 #pragma unroll
@@ -369,6 +373,105 @@ __global__ __launch_bounds__(256) void k_diag_d0(int n, int k, const double* __r
     }
 }
 
+// kt_entries_fun: the sweep's terms of f(A) entries on a pair list.  The
+// DiagGeo<P> geometry per PAIR: LPR lanes own pair e = tab[e] = (r_i, r_j, i,
+// j) (rows of Y and Q in the sweep's order, original indices for the signs),
+// each lane with its 16-byte probe pair of both rows.  With yt = y - Q c in
+// the fma order of k_diag_finish, t = (z_i yt_j + z_j yt_i) / 2 and t^2 are
+// reduced over the pair's probes by the butterfly of row_sum and added to
+// esum[e] / esum2[e] by the group's lane 0 (every pair has its own slot: no
+// atomics).  Dead lanes of a tail group carry zeros through the butterfly; a
+// remainder sweep's dead columns are zero columns of Y and c.
+template <int P, int KP>
+__global__ __launch_bounds__(kDiagBlock) void k_entries_accumulate(int64_t npairs, const int4* __restrict__ tab,
+                                                                   uint64_t seed, int64_t base,
+                                                                   const double* __restrict__ Q,
+                                                                   const double* __restrict__ c,
+                                                                   const double* __restrict__ Y,
+                                                                   double* __restrict__ esum,
+                                                                   double* __restrict__ esum2) {
+    using G = DiagGeo<P>;
+    const int sub = threadIdx.x % G::LPR;
+    uint64_t key[G::VEC];
+    probe_keys<P>(seed, base, sub, key);
+    double cc[KP > 0 ? KP : 1][G::VEC];
+#pragma unroll
+    for (int b = 0; b < KP; ++b)
+#pragma unroll
+        for (int v = 0; v < G::VEC; ++v) cc[b][v] = c[b * P + sub * G::VEC + v];
+    for (int64_t eb = (int64_t)blockIdx.x * G::RPB; eb < npairs; eb += (int64_t)gridDim.x * G::RPB) {
+        const int64_t e = eb + threadIdx.x / G::LPR;
+        const bool live = e < npairs;
+        double yi[G::VEC], yj[G::VEC], si[G::VEC], sj[G::VEC];
+#pragma unroll
+        for (int v = 0; v < G::VEC; ++v) yi[v] = yj[v] = si[v] = sj[v] = 0.0;
+        int4 pe = {0, 0, 0, 0};
+        if (live) {
+            pe = tab[e];
+            ld_vec<G::VEC>(Y + (int64_t)pe.x * P + sub * G::VEC, yi);
+            ld_vec<G::VEC>(Y + (int64_t)pe.y * P + sub * G::VEC, yj);
+            if constexpr (KP > 0) {
+                const double* qi = Q + (int64_t)pe.x * KP;
+                const double* qj = Q + (int64_t)pe.y * KP;
+#pragma unroll
+                for (int b = 0; b < KP; ++b) {
+                    const double qib = qi[b], qjb = qj[b];
+#pragma unroll
+                    for (int v = 0; v < G::VEC; ++v) {
+                        si[v] = fma(qib, cc[b][v], si[v]);
+                        sj[v] = fma(qjb, cc[b][v], sj[v]);
+                    }
+                }
+            }
+        }
+        double t[G::VEC], t2[G::VEC];
+#pragma unroll
+        for (int v = 0; v < G::VEC; ++v) {
+            const double zi = probe_sign(key[v], (uint64_t)pe.z), zj = probe_sign(key[v], (uint64_t)pe.w);
+            t[v] = 0.5 * (zi * (yj[v] - sj[v]) + zj * (yi[v] - si[v]));
+            t2[v] = t[v] * t[v];
+        }
+        const double s1 = row_sum<P>(t), s2 = row_sum<P>(t2);
+        if (live && sub == 0) {
+            esum[e] += s1;
+            esum2[e] += s2;
+        }
+    }
+}
+
+// e0[e] = sum_c (Q[i, c] G[j, c] + G[i, c] Q[j, c])
+//         - (sum_c (QH)[i, c] Q[j, c] + (QH)[j, c] Q[i, c]) / 2,  (i, j) = tab[e].zw
+// (Q, G n x ld row-major in original row numbering; H k x k column-major).
+// Each column's two products are rounded and added symmetrically, so (i, j)
+// and (j, i) give the same bits.
+__global__ __launch_bounds__(256) void k_entries_e0(int64_t npairs, const int4* __restrict__ tab, int k,
+                                                    const double* __restrict__ Q, const double* __restrict__ G,
+                                                    int ld, const double* __restrict__ H,
+                                                    double* __restrict__ e0) {
+    __shared__ double sH[16 * 16];
+    for (int i = threadIdx.x; i < k * k; i += blockDim.x) sH[i] = H[i];
+    __syncthreads();
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < npairs;
+         e += (int64_t)gridDim.x * blockDim.x) {
+        const int4 pe = tab[e];
+        const double* qi = Q + (int64_t)pe.z * ld;
+        const double* qj = Q + (int64_t)pe.w * ld;
+        const double* gi = G + (int64_t)pe.z * ld;
+        const double* gj = G + (int64_t)pe.w * ld;
+        double a = 0.0, b2 = 0.0;
+        for (int c = 0; c < k; ++c) {
+            a += __dadd_rn(__dmul_rn(qi[c], gj[c]), __dmul_rn(gi[c], qj[c]));
+            double hi = 0.0, hj = 0.0;
+            for (int b = 0; b < k; ++b) {
+                hi = fma(qi[b], sH[b + c * k], hi);
+                hj = fma(qj[b], sH[b + c * k], hj);
+            }
+            b2 += __dadd_rn(__dmul_rn(hi, qj[c]), __dmul_rn(hj, qi[c]));
+        }
+        e0[e] = a - 0.5 * b2;
+    }
+}
+
 template <class F> hipError_t by_width(int P, F&& f) {
     switch (P) {
         case 1: return f(std::integral_constant<int, 1>{});
@@ -444,6 +547,47 @@ hipError_t launch_diag_combine(int P, int KP, int grid, int n, int m, int mdepth
             return hipGetLastError();
         });
     });
+}
+
+hipError_t launch_diag_combine_y(int P, int grid, int n, int m, int mdepth, const double* V, int64_t sstride,
+                                 const double* W, const int* depth, double* Y, hipStream_t st) {
+    const size_t lds = sizeof(double) * (size_t)m * P;
+    return by_width(P, [&](auto p) {
+        k_diag_combine<decltype(p)::value, 0, true><<<grid, kDiagBlock, lds, st>>>(
+            n, m, mdepth, V, sstride, W, depth, 0, 0, nullptr, nullptr, Y, nullptr, nullptr, nullptr);
+        return hipGetLastError();
+    });
+}
+
+int entries_grid(int64_t npairs, int P) {
+    const int vec = P >= 2 ? 2 : 1, ppb = kDiagBlock / (P / vec);
+    return (int)std::max<int64_t>(1, std::min<int64_t>((npairs + ppb - 1) / ppb, 4096));
+}
+
+hipError_t launch_entries_accumulate(int P, int KP, int64_t npairs, const void* tab, uint64_t seed, int64_t base,
+                                     const double* Q, const double* c, const double* Y, double* esum,
+                                     double* esum2, hipStream_t st) {
+    const int grid = entries_grid(npairs, P);
+    const int4* t = static_cast<const int4*>(tab);
+    return by_width(P, [&](auto p) {
+        constexpr int PP = decltype(p)::value;
+        if (KP == 0) {
+            k_entries_accumulate<PP, 0><<<grid, kDiagBlock, 0, st>>>(npairs, t, seed, base, Q, c, Y, esum, esum2);
+            return hipGetLastError();
+        }
+        return by_defl(KP, [&](auto k) {
+            k_entries_accumulate<PP, decltype(k)::value>
+                <<<grid, kDiagBlock, 0, st>>>(npairs, t, seed, base, Q, c, Y, esum, esum2);
+            return hipGetLastError();
+        });
+    });
+}
+
+hipError_t launch_entries_e0(int64_t npairs, const void* tab, int k, const double* Q, const double* G, int ld,
+                             const double* H, double* e0, hipStream_t st) {
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((npairs + 255) / 256, 2048));
+    k_entries_e0<<<grid, 256, 0, st>>>(npairs, static_cast<const int4*>(tab), k, Q, G, ld, H, e0);
+    return hipGetLastError();
 }
 
 hipError_t launch_diag_finish(int P, int KP, int grid, int n, uint64_t seed, int64_t base, const int* perm,

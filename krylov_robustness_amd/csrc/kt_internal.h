@@ -137,10 +137,11 @@ struct ProfSlot {
 // launch is also one of the sweep's step passes in PROF_SPMM.  PROF_CHECK:
 // the stopping test of an error-controlled SLQ sweep (k_quad_check_wide).
 // PROF_DIAG / PROF_DIAG_START: kt_diag_fun's combine + accumulate kernels and
-// its start-block kernels (kt_diag.hip)
+// its start-block kernels (kt_diag.hip); kt_entries_fun's sweeps report in the
+// same two.  PROF_ENTRIES: its pair kernels (k_entries_accumulate, k_entries_e0)
 enum {
     PROF_SPMM = 0, PROF_UPDATE = 1, PROF_START = 2, PROF_YBLOCK = 3, PROF_EXPMV = 4, PROF_FIRST = 5,
-    PROF_CHECK = 6, PROF_DIAG = 7, PROF_DIAG_START = 8, PROF_NSLOTS = 9
+    PROF_CHECK = 6, PROF_DIAG = 7, PROF_DIAG_START = 8, PROF_ENTRIES = 9, PROF_NSLOTS = 10
 };
 
 // Buffers of one probe-sweep lane (kt_slq.cpp); two lanes let two sweeps

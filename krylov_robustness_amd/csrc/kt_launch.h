@@ -212,6 +212,19 @@ hipError_t launch_diag_finish(int P, int KP, int grid, int n, uint64_t seed, int
 // d0 = 2 rowsum(Q .* G) - rowsum((Q H) .* Q); Q, G n x ld row-major, H k x k column-major
 hipError_t launch_diag_d0(int n, int k, const double* Q, const double* G, int ld, const double* H, double* d0,
                           hipStream_t st);
+// f(A) entries on a pair list (kt_entries_fun).  tab: npairs x (r_i, r_j, i, j)
+// int32, rows in the sweep's order and original indices.  launch_diag_combine_y
+// is launch_diag_combine's KP = 0 pass storing y into Y (no sums);
+// launch_entries_accumulate adds the sweep's sum_p t and sum_p t^2 to esum /
+// esum2 (Y, Q in the sweep's row order, c = Q'y: KP x P); launch_entries_e0
+// forms the exact deflated part (Q, G in original numbering, H k x k column-major).
+hipError_t launch_diag_combine_y(int P, int grid, int n, int m, int mdepth, const double* V, int64_t sstride,
+                                 const double* W, const int* depth, double* Y, hipStream_t st);
+hipError_t launch_entries_accumulate(int P, int KP, int64_t npairs, const void* tab, uint64_t seed, int64_t base,
+                                     const double* Q, const double* c, const double* Y, double* esum,
+                                     double* esum2, hipStream_t st);
+hipError_t launch_entries_e0(int64_t npairs, const void* tab, int k, const double* Q, const double* G, int ld,
+                             const double* H, double* e0, hipStream_t st);
 int inf_norm_blocks();
 // normest1 (t = 1) reductions, normest1_blocks(n) partials each: sum |Y| in
 // partial[0, nb), S_prev . S in partial[nb, 2 nb), S = mysign(Y); per-block

@@ -155,18 +155,22 @@ def _stable_head(key, num):
     return cand[np.argsort(key[cand], kind="stable")][:num]
 
 
-def find_top_edges(A, centrality, num, order="mult"):
-    """find_top_edges.m:1-40: the top `num` existing edges (1-based, i > j)."""
+def _tril_edges(A):
+    """[I, J] = find(tril(A, -1)), 0-based, in column-major order, read
+    straight off the CSC arrays."""
     import scipy.sparse as sp
     L = A if sp.isspmatrix_csc(A) else sp.csc_matrix(A)
     if not L.has_canonical_format:  # duplicates summed (tril(A) sees sums), sorted
         L = L.copy()
         L.sum_duplicates()
-    # find(tril(A, -1)) in column-major order, read straight off the CSC arrays
     J = np.repeat(np.arange(L.shape[1], dtype=np.int64), np.diff(L.indptr))
     keep = (L.indices > J) & (L.data != 0)
-    I = L.indices[keep].astype(np.int64)
-    J = J[keep]
+    return L.indices[keep].astype(np.int64), J[keep]
+
+
+def find_top_edges(A, centrality, num, order="mult"):
+    """find_top_edges.m:1-40: the top `num` existing edges (1-based, i > j)."""
+    I, J = _tril_edges(A)
     c = np.asarray(centrality, dtype=np.float64).ravel()
     if order == "mult":  # :22-25
         key = -(c[I] * c[J])
@@ -189,6 +193,31 @@ def find_top_edges(A, centrality, num, order="mult"):
     if len(I) < num:
         raise IndexError("FIND_TOP_EDGES:: there are not enough edges in the graph")
     ind = _stable_head(key, num)
+    return np.stack([I[ind] + 1, J[ind] + 1], axis=1)
+
+
+def find_top_edges_fun(A, num, fun="exp", nprobes=256, deflate=1, m=30, seed=0, ctx: Optional[Context] = None):
+    """The top `num` existing edges ranked by descending estimated f(A)[i, j]
+    (entries_fun on every edge: one sweep set however many edges), returned as
+    find_top_edges returns them: 1-based, i > j, enumerated in find(tril(A,
+    -1)) order with ties kept in that order, and the same warning / error when
+    fewer than `num` edges exist.  To first order, editing edge (i, j) changes
+    tr f(A) by -/+ 2 f'(A)[i, j]: for f = exp the ranking is by that
+    derivative; for a general f pass its derivative's code as `fun` (sinh to
+    rank for cosh and the reverse).  Missing edges are O(n^2): score a
+    candidate list of them with entries_fun."""
+    from .core import entries_fun
+    D = _dev(A, ctx)
+    I, J = _tril_edges(D.to_scipy())
+    if len(I) < num:
+        warnings.warn("FIND_TOP_EDGES:: there are not enough edges in the graph")
+    num = int(np.floor(num))
+    if len(I) < num:
+        raise IndexError("FIND_TOP_EDGES:: there are not enough edges in the graph")
+    if len(I) == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    est = entries_fun(D, np.stack([I, J], axis=1), nprobes, m=m, seed=seed, fun=fun, deflate=deflate, ctx=ctx)
+    ind = _stable_head(-np.asarray(est.mean, dtype=np.float64), num)
     return np.stack([I[ind] + 1, J[ind] + 1], axis=1)
 
 
@@ -298,10 +327,12 @@ def _is_symmetric(S):
 
 
 def greedy_krylov(A, k, Q=0, centrality=None, order="mult", tol=1e-12, it=None, poles=np.inf,
-                  debug=0, miobi="break", rescale=1.0, ctx: Optional[Context] = None):
+                  debug=0, miobi="break", rescale=1.0, ctx: Optional[Context] = None, top=None):
     """[edges, rob_variation, A_new] = greedy_krylov(A, k, Q, centrality, order, tol, it,
     poles, debug, miobi, rescale)  (greedy_krylov.m:1-100).  Returns A_new as
-    the DeviceMatrix the edits were applied to (``.to_scipy()`` for the host copy)."""
+    the DeviceMatrix the edits were applied to (``.to_scipy()`` for the host copy).
+    top: a ranked list of 1-based pairs (e.g. find_top_edges_fun's) used in
+    place of the find_top_* call; centrality and order are then not read."""
     D = _dev(A, ctx)
     S = D.to_scipy()
     if not _is_symmetric(S):  # :27-29
@@ -317,10 +348,13 @@ def greedy_krylov(A, k, Q=0, centrality=None, order="mult", tol=1e-12, it=None, 
     Q = int(np.floor(Q))
     if miobi == "break" and S.nnz < 2 * k:  # :54-56
         raise _lib.KrylovError(_lib.KT_ERR_ARG, "GREEDY_KRYLOV:: edges to be removed are more than edges in the network")
-    if centrality is None:
-        centrality = compute_centrality(D, "eig", ctx=ctx)
-    top = (find_top_missing_edges(S, centrality, Qn, order) if miobi == "make"
-           else find_top_edges(S, centrality, Qn, order))  # :82 (first step)
+    if top is not None:
+        top = np.asarray(top, dtype=np.int64).reshape(-1, 2)
+    else:
+        if centrality is None:
+            centrality = compute_centrality(D, "eig", ctx=ctx)
+        top = (find_top_missing_edges(S, centrality, Qn, order) if miobi == "make"
+               else find_top_edges(S, centrality, Qn, order))  # :82 (first step)
     if len(top) >= int(k) > 0 and int(Q) >= 1:
         # the step loop in the library (kt_greedy_krylov_steps): krylov_miobi(A, 1,
         # top(1:Q)) per step, the selected pair dropped from the ranking (:84-89)

@@ -5,9 +5,9 @@
 //   start    z' = z - Q (Q'z) and ||z'||^2 (k_diag_qtz, k_diag_start; z comes
 //            from the counter RNG in registers, Q'z from workgroup partials
 //            summed in a fixed order)
-//   sweep    a y-form sweep that forms its own Lanczos basis (YBlockSweep with
-//            `basis`); one whose cancellation guard trips, or that breaks
-//            down, is redone whole by the explicit CGS2 sweep with its basis
+//   sweep    a y-form sweep that forms its own Lanczos basis (a block-seeded
+//            YSweep with `basis`); one whose cancellation guard trips, or that
+//            breaks down, is redone whole by the explicit CGS2 sweep with its basis
 //            (KT_SLQ_YFORM=0, the hot path's switch: every sweep explicit)
 //   weights  host pool: ||z'|| f(T) e1 per column from its record, cut at a
 //            lucky breakdown; the m x P table and the cuts go back
@@ -144,8 +144,7 @@ void probe_sweeps(const std::string& who, kt_matrix_s* A, int fun, int m, uint64
 
     const int64_t nsw = (nprobes + P - 1) / P;
     // KT_SLQ_LANES=L (<= 4), as the y-form sweeps of kt_slq_trace: 2 by default
-    const char* le = getenv("KT_SLQ_LANES");
-    const int lanes_env = le ? std::max(1, std::min(4, atoi(le))) : 2;
+    const int lanes_env = std::max(1, std::min(4, slq_lanes_env(2)));
     int lanes = (int)std::max<int64_t>(1, std::min<int64_t>(nsw, lanes_env));
     const int grid = diag_grid(n, P), KK = std::max(KP, 1);
     std::vector<DiagLane> L(lanes);
@@ -168,9 +167,7 @@ void probe_sweeps(const std::string& who, kt_matrix_s* A, int fun, int m, uint64
         d.n2 = d.c + (size_t)KK * P;
         d.W = d.n2 + P;
         d.depth = reinterpret_cast<int*>(d.W + (size_t)m * P);
-        if (l && !ctx->aux_stream[l - 1])
-            KT_HIP(hipStreamCreateWithFlags(&ctx->aux_stream[l - 1], hipStreamNonBlocking));
-        d.st = l ? ctx->aux_stream[l - 1] : ctx->stream;
+        d.st = lane_stream(ctx, l);
     }
     // the sums, alive for the call; added to in sweep order on ctx->stream
     steps.prepare();
@@ -188,8 +185,7 @@ void probe_sweeps(const std::string& who, kt_matrix_s* A, int fun, int m, uint64
         auto live_of = [&](int l) { return (int)std::min<int64_t>(P, nprobes - (s0 + l) * P); };
         auto host_of = [&](int l) { return pin.as<double>() + per * l; };
         // start blocks and sweeps, the lanes' launches queued side by side
-        std::vector<std::unique_ptr<YBlockSweep>> ys;
-        std::vector<std::unique_ptr<ExplicitSweep>> ex;  // KT_SLQ_YFORM=0: every sweep explicit (the A/B)
+        SweepList grp;
         for (int l = 0; l < g; ++l) {
             DiagLane& d = L[l];
             const int nc = live_of(l);
@@ -204,32 +200,19 @@ void probe_sweeps(const std::string& who, kt_matrix_s* A, int fun, int m, uint64
             prof_end(ctx, PROF_DIAG_START, d.st);
             KT_HIP(hipMemcpyAsync(host_of(l) + rec, d.n2, sizeof(double) * P, hipMemcpyDeviceToHost, d.st));
             if (ctx->yform)
-                ys.emplace_back(
-                    new YBlockSweep(A, M, P, m, d.x.col(0), P, nc, d.n2, host_of(l), l, d.basis.col(0), nc));
-            else
-                ex.emplace_back(new ExplicitSweep(A, M, P, m, 0, 0, d.x.col(0), P, nc, d.n2, host_of(l), &d.basis,
-                                                  &hists[l], l, P));
+                grp.emplace_back(new YSweep(A, M, P, m, d.x.col(0), P, nc, d.n2, host_of(l), l, d.basis.col(0), nc));
+            else  // KT_SLQ_YFORM=0: every sweep explicit (the A/B)
+                grp.emplace_back(new ExplicitSweep(A, M, P, m, 0, 0, d.x.col(0), P, nc, d.n2, host_of(l), &d.basis,
+                                                   &hists[l], l, P));
         }
-        for (auto& y : ys) y->start();
-        for (auto& e : ex) e->start();
-        for (int j = 0; j < m; ++j) {
-            for (auto& y : ys)
-                if (j + 1 < m) y->step(j);
-            for (auto& e : ex) e->step(j);
-        }
-        for (auto& y : ys) y->finish();
-        for (auto& e : ex) e->finish();
+        run_sweeps(grp);
         for (int l = 0; l < g; ++l) KT_HIP(hipStreamSynchronize(L[l].st));
         // a sweep with a guarded (or broken-down) column: redone whole by the
         // explicit sweep with its basis (slot j = u_j, n x P; v_j = s_j u_j)
         std::vector<char> explicit_basis(g, ctx->yform ? 0 : 1);
         for (int l = 0; l < g && ctx->yform; ++l) {
             double* R = host_of(l);
-            const double* gd = R + (size_t)3 * m * P;
-            const double* n2 = R + rec;
-            bool bad = false;
-            for (int c = 0; c < live_of(l); ++c) bad |= n2[c] > 0.0 && !(gd[c] >= kYformGuard);
-            if (!bad) continue;
+            if (!guard_tripped(R, m, P, live_of(l), R + rec)) continue;
             DiagLane& d = L[l];
             lanczos_sweep(A, M, P, m, 0, 0, d.x.col(0), P, live_of(l), d.n2, R, &d.basis, &hists[l], l, P);
             KT_HIP(hipStreamSynchronize(d.st));
@@ -248,12 +231,11 @@ void probe_sweeps(const std::string& who, kt_matrix_s* A, int fun, int m, uint64
             dep[c] = 0;
             if (c >= live_of(l) || !(n2[c] > 0.0)) return;
             std::vector<double> al(m), off(m), fe1(m);
-            const int steps = record_tridiag(R, m, P, c, al.data(), off.data());
+            const int steps = record_tridiag(R, m, m, P, c, al.data(), off.data());
             const double qd = tridiag_fun_e1(steps, al.data(), off.data(), fun, fe1.data());
             qv[(size_t)((s0 + l) * P + c)] = n2[c] * qd;
-            const double nx = std::sqrt(n2[c]);
-            for (int j = 0; j < steps; ++j)
-                W[(size_t)j * P + c] = explicit_basis[l] ? nx * hists[l][(size_t)j * P + c] * fe1[j] : nx * fe1[j];
+            basis_weights(steps, std::sqrt(n2[c]), fe1.data(), explicit_basis[l] ? hists[l].data() + c : nullptr, P,
+                          W + c, P);
             dep[c] = steps;
         }, 4);
         // combine and accumulate, every sweep on ctx->stream in sweep order

@@ -41,40 +41,54 @@ int slq_auto_block(int64_t n, int64_t nprobes) {
     return P;
 }
 
+hipStream_t lane_stream(kt_context_s* ctx, int lane) {
+    if (lane < 0 || lane > 3) fail(KT_ERR_ARG, "sweep lane out of range");
+    if (lane && !ctx->aux_stream[lane - 1])
+        KT_HIP(hipStreamCreateWithFlags(&ctx->aux_stream[lane - 1], hipStreamNonBlocking));
+    return lane ? ctx->aux_stream[lane - 1] : ctx->stream;
+}
+
+SweepLane::SweepLane(kt_matrix_s* A, const DevCSR& M, int P, int lane)
+    : st(lane_stream(A->ctx, lane)),
+      grid(spmm_grid((int)A->n, P, A->ctx->num_cu * 4)),  // 4 row-group workgroups per CU
+      lblocks(long_blocks_for(M.n_long, A->ctx->num_cu * 2)),
+      grid1(grid + lblocks),
+      blk_bytes(sizeof(double) * (size_t)A->n * P),
+      w(A->ctx->ws.sweep[lane]) {}
+
+void run_sweeps(const SweepList& sweeps) {
+    int steps = 0;
+    for (auto& s : sweeps) {
+        s->start();
+        steps = std::max(steps, s->nsteps());
+    }
+    for (int j = 0; j < steps; ++j)
+        for (auto& s : sweeps)
+            if (j < s->nsteps()) s->step(j);
+    for (auto& s : sweeps) s->finish();
+}
+
 // Run one sweep.  rec_host receives [alpha | up | low][m][P].
 // init: if seeded by RNG, `x` == nullptr; else x (device, n x ldx, ncols
 // columns, their squared norms in the DEVICE array dnorms2) is copied into
-// the sweep block.  ExplicitSweep enqueues it step by step, so sweeps on
-// different lanes can be queued launch by launch (the runtime throttles a
-// long enqueue burst to ~58 us per call once the host runs ~1 ms ahead, so
-// a second lane queued after a whole first sweep would start ms late).
+// the sweep block.
 ExplicitSweep::ExplicitSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, uint64_t seed_, int64_t probe_base_,
                              const double* x_, int ldx_, int ncols_, const double* dnorms2_, double* rec_host_,
                              DevMat* basis_, std::vector<double>* scale_hist_, int lane_, int bcols_)
     : A(A_), M(M_), P(P_), m(m_), seed(seed_), probe_base(probe_base_), x(x_), ldx(ldx_), ncols(ncols_),
-      dnorms2(dnorms2_), rec_host(rec_host_), basis(basis_), scale_hist(scale_hist_), lane(lane_), bcols(bcols_) {
-    if (bcols <= 0 || bcols > P) bcols = P;
-    kt_context_s* ctx = A->ctx;
-    n = (int)A->n;
-    if (lane < 0 || lane > 3) fail(KT_ERR_ARG, "sweep lane out of range");
-    if (lane && !ctx->aux_stream[lane - 1])
-        KT_HIP(hipStreamCreateWithFlags(&ctx->aux_stream[lane - 1], hipStreamNonBlocking));
-    st = lane ? ctx->aux_stream[lane - 1] : ctx->stream;
-    grid = spmm_grid(n, P, ctx->num_cu * 4);  // K2 / short rows
-    lblocks = long_blocks_for(M.n_long, ctx->num_cu * 2);
-    grid1 = grid + lblocks;                    // K1 total
-    SweepBufs& w = ctx->ws.sweep[lane];
-    blk_bytes = sizeof(double) * (size_t)n * P;
-    w.X0.ensure(blk_bytes);
-    w.X1.ensure(blk_bytes);
-    w.Y.ensure(blk_bytes);
-    w.partial.ensure(sizeof(double) * (size_t)(grid1 + grid * 3) * P);
+      dnorms2(dnorms2_), rec_host(rec_host_), basis(basis_), scale_hist(scale_hist_),
+      bcols((bcols_ <= 0 || bcols_ > P_) ? P_ : bcols_), n((int)A_->n), L(A_, M_, P_, lane_) {
+    SweepBufs& w = L.w;
+    w.X0.ensure(L.blk_bytes);
+    w.X1.ensure(L.blk_bytes);
+    w.Y.ensure(L.blk_bytes);
+    w.partial.ensure(sizeof(double) * (size_t)(L.grid1 + L.grid * 3) * P);
     w.k2s.ensure(sizeof(double) * 4 * P);
     w.coef.ensure(sizeof(double) * 2 * P);
     w.scales.ensure(sizeof(double) * 3 * P);
     w.trec.ensure(sizeof(double) * (size_t)3 * m * P);
     part1 = w.partial.as<double>();
-    part2 = part1 + (size_t)grid1 * P;
+    part2 = part1 + (size_t)L.grid1 * P;
     k2s = w.k2s.as<double>();
     coef = w.coef.as<double>();
     trec = w.trec.as<double>();
@@ -87,13 +101,13 @@ ExplicitSweep::ExplicitSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, 
 }
 
 void ExplicitSweep::start() {
-    kt_context_s* ctx = A->ctx;
+    hipStream_t st = L.st;
     if (!x) {
         KT_HIP(launch_rademacher(P, n, seed, probe_base, M.perm, ucur, st));
         KT_HIP(launch_fill(sc, P, 1.0 / std::sqrt((double)n), st));
         KT_HIP(launch_fill(k2s, P, (double)n, st));  // ||z||^2 = n
     } else {
-        KT_HIP(hipMemsetAsync(ucur, 0, blk_bytes, st));
+        KT_HIP(hipMemsetAsync(ucur, 0, L.blk_bytes, st));
         KT_HIP(hipMemcpy2DAsync(ucur, sizeof(double) * P, x, sizeof(double) * ldx, sizeof(double) * ncols, (size_t)n,
                                 hipMemcpyDeviceToDevice, st));
         // s_0 = 1/||x_c||, ||x_c||^2 from the device norms: no host round trip
@@ -101,7 +115,7 @@ void ExplicitSweep::start() {
     }
     if (scale_hist) {
         scale_hist->assign((size_t)m * P, 0.0);
-        hist_dev = &ctx->ws.sweep[lane].hist;
+        hist_dev = &L.w.hist;
         hist_dev->ensure(sizeof(double) * (size_t)m * P);
     }
     // basis slot j (u_j's first bcols columns, n x bcols row-major) at
@@ -129,13 +143,14 @@ double* ExplicitSweep::slot(int j) {
 
 void ExplicitSweep::step(int j) {
     kt_context_s* ctx = A->ctx;
-    const int first = (j == 0);
+    hipStream_t st = L.st;
+    const int first = (j == 0), grid = L.grid, grid1 = L.grid1;
     if ((basis || chunks) && first)  // u_0 into slot 0
         KT_HIP(hipMemcpy2DAsync(slot(0), sizeof(double) * bcols, ucur, sizeof(double) * P, sizeof(double) * bcols,
                                 (size_t)n, hipMemcpyDeviceToDevice, st));
     prof_begin(ctx, PROF_SPMM, st, P);
     KT_HIP(launch_spmm_dot(P, ctx->k1_flags | (A->unit_values ? 2 : 0), grid1, M.rowptr, M.col, M.val, n, ucur, sc, Yb,
-                           part1, M.long_rows, M.n_long, A->long_thresh, lblocks, st));
+                           part1, M.long_rows, M.n_long, A->long_thresh, L.lblocks, st));
     prof_end(ctx, PROF_SPMM, st);
     // the coefficient launch also records s_j (v_j = s_j u_j) for a basis sweep
     KT_HIP(launch_coef_cgs2(P, part1, grid1, first, k2s, sc, sp, coef, trec + (size_t)(0 * m + j) * P,
@@ -154,52 +169,63 @@ void ExplicitSweep::step(int j) {
 }
 
 void ExplicitSweep::finish() {
-    KT_HIP(hipMemcpyAsync(rec_host, trec, sizeof(double) * (size_t)3 * m * P, hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(rec_host, trec, sizeof(double) * (size_t)3 * m * P, hipMemcpyDeviceToHost, L.st));
     if (scale_hist)
         KT_HIP(hipMemcpyAsync(scale_hist->data(), hist_dev->ptr, sizeof(double) * (size_t)m * P,
-                              hipMemcpyDeviceToHost, st));
+                              hipMemcpyDeviceToHost, L.st));
 }
 
 void ExplicitSweep::finish(int rows) {
     if (rows <= 0) return;
     // the three record blocks' first `rows` rows, at the capacity's stride
     KT_HIP(hipMemcpy2DAsync(rec_host, sizeof(double) * (size_t)m * P, trec, sizeof(double) * (size_t)m * P,
-                            sizeof(double) * (size_t)rows * P, 3, hipMemcpyDeviceToHost, st));
+                            sizeof(double) * (size_t)rows * P, 3, hipMemcpyDeviceToHost, L.st));
     if (scale_hist)
         KT_HIP(hipMemcpyAsync(scale_hist->data(), hist_dev->ptr, sizeof(double) * (size_t)rows * P,
-                              hipMemcpyDeviceToHost, st));
+                              hipMemcpyDeviceToHost, L.st));
 }
 
 void lanczos_sweep(kt_matrix_s* A, const DevCSR& M, int P, int m, uint64_t seed, int64_t probe_base,
                    const double* x, int ldx, int ncols, const double* dnorms2, double* rec_host,
                    DevMat* basis, std::vector<double>* scale_hist, int lane, int bcols) {
-    ExplicitSweep s(A, M, P, m, seed, probe_base, x, ldx, ncols, dnorms2, rec_host, basis, scale_hist, lane, bcols);
-    s.start();
-    for (int j = 0; j < m; ++j) s.step(j);
-    s.finish();
+    SweepList one;
+    one.emplace_back(
+        new ExplicitSweep(A, M, P, m, seed, probe_base, x, ldx, ncols, dnorms2, rec_host, basis, scale_hist, lane, bcols));
+    run_sweeps(one);
 }
 
-// y-form sweep (RNG-seeded probes only): one fused pass + one coefficient
-// launch per Lanczos step (kt_kernels.hip, k_spmm_lanczos / k_ycoef).
-// rec_host receives [alpha | up | low][m][P] followed by guard[P].  Enqueued
-// step by step (start(), step(j) for j < m - 1, finish()), so sweeps on
-// different lanes are queued launch by launch.
+// y-form sweep: one fused pass + one coefficient launch per Lanczos step
+// (kt_kernels.hip, k_spmm_lanczos / k_ycoef).  rec_host (pinned, or the call
+// waits for the copy) receives [alpha | up | low][m][P] followed by guard[P].
+// The block seed (the quadrature-only columns of mc_trace's Lanczos Afun,
+// kt_mctrace.cpp; kt_diag_fun's sweeps): x (n x ldx, ncols columns, in M's row
+// order, squared norms in the device array dnorms2) is normalised into the
+// gathered table v_0 (zero columns stay zero), the pass in start mode forms
+// y_0 = A v_0 with (g, a, b) = (1, 0, 0), then the same passes as the
+// sign-seeded sweep (steps 0 .. m-2).
 YSweep::YSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, uint64_t seed_, int64_t probe_base_,
                double* rec_host_, int lane_, bool int0_, const int* gate_, int ngate_)
-    : A(A_), M(M_), P(P_), m(m_), seed(seed_), probe_base(probe_base_), rec_host(rec_host_), lane(lane_),
-      int0(int0_), gate(gate_), ngate(ngate_) {
-    kt_context_s* ctx = A->ctx;
-    n = (int)A->n;
-    if (lane < 0 || lane > 3) fail(KT_ERR_ARG, "sweep lane out of range");
+    : A(A_), M(M_), P(P_), m(m_), n((int)A_->n), rec_host(rec_host_), L(A_, M_, P_, lane_), seed(seed_),
+      probe_base(probe_base_), int0(int0_), gate(gate_), ngate(ngate_) {
+    s0 = 1.0 / std::sqrt((double)n);  // v_0 = z / ||z||, ||z||^2 = n
+    setup();
+}
+
+YSweep::YSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, const double* x_, int ldx_, int ncols_,
+               const double* dnorms2_, double* rec_host_, int lane_, double* basis_, int bcols_)
+    : A(A_), M(M_), P(P_), m(m_), n((int)A_->n), rec_host(rec_host_), L(A_, M_, P_, lane_), x(x_), ldx(ldx_),
+      ncols(ncols_), dnorms2(dnorms2_), basis(basis_), bcols(basis_ ? bcols_ : 0) {
+    if (!x) fail(KT_ERR_ARG, "y-form block sweep: x is NULL");
+    if (ncols < 1 || ncols > P) fail(KT_ERR_ARG, "y-form block sweep: 1 <= ncols <= P");
+    setup();
+}
+
+void YSweep::setup() {
     if (!M.lower) fail(KT_ERR_ARG, "y-form sweep: the CSR copy has no lower-prefix array");
-    if (lane && !ctx->aux_stream[lane - 1])
-        KT_HIP(hipStreamCreateWithFlags(&ctx->aux_stream[lane - 1], hipStreamNonBlocking));
-    st = lane ? ctx->aux_stream[lane - 1] : ctx->stream;
-    grid = spmm_grid(n, P, ctx->num_cu * 4);  // 4 row-group workgroups per CU
-    lblocks = long_blocks_for(M.n_long, ctx->num_cu * 2);
-    grid1 = grid + lblocks;
-    SweepBufs& w = ctx->ws.sweep[lane];
-    blk_bytes = sizeof(double) * (size_t)n * P;
+    if (gate && basis) fail(KT_ERR_ARG, "y-form sweep: the gated form keeps no basis");
+    if (int0 && x) fail(KT_ERR_ARG, "y-form sweep: the int16 start needs the sign seed");
+    SweepBufs& w = L.w;
+    const size_t blk_bytes = L.blk_bytes;
     // X1: the packed sign table and, in the compact form, y_0's int16 table
     // behind it (not in y_0's own slot Y: the second step stores y_2 there
     // while other rows still read y_0, and the two layouts' rows do not
@@ -208,45 +234,63 @@ YSweep::YSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, uint64_t seed_
     w.X0.ensure(blk_bytes);
     w.X1.ensure(int0 ? std::max(blk_bytes, t0_off + sizeof(int16_t) * (size_t)n * P) : blk_bytes);
     w.Y.ensure(blk_bytes);
-    w.partial.ensure(sizeof(double) * (size_t)3 * P * grid1);  // slot-major [3P][grid1]
+    w.partial.ensure(sizeof(double) * (size_t)3 * P * L.grid1);  // slot-major [3P][grid1]
     w.coef.ensure(sizeof(double) * 9 * P);
     w.trec.ensure(sizeof(double) * ((size_t)3 * m * P + P));
     part = w.partial.as<double>();
     ys = w.coef.as<double>();
     trec = w.trec.as<double>();
     guard = trec + (size_t)3 * m * P;
-    flags = ctx->ky_flags | (A->unit_values ? 2 : 0);
+    flags = A->ctx->ky_flags | (A->unit_values ? 2 : 0);
     if (blk_bytes >= ((size_t)1 << 31)) flags &= ~16;  // sc1 buffer stores take 32-bit offsets
     Z = w.X1.as<uint32_t>();
     if (int0) T0 = reinterpret_cast<int16_t*>(w.X1.as<char>() + t0_off);
+    V0 = basis ? slot(0) : w.X1.as<double>();
     Xc = w.Y.as<double>();   // y_j (compact form: y_0 is T0, this slot is first used for y_2)
     Yo = nullptr;            // y_{j-1} (none at j = 0)
     Ot = w.X0.as<double>();  // y_{j+1}
-    s0 = 1.0 / std::sqrt((double)n);  // v_0 = z / ||z||, ||z||^2 = n
 }
 
 void YSweep::start() {
     kt_context_s* ctx = A->ctx;
-    // probes as a packed sign table (n x ceil(P/32) words), gathered by the
-    // start pass instead of an 8nP-byte fp64 block
-    KT_HIP(launch_rademacher_signs(P, n, seed, probe_base, M.perm, Z, st));
-    prof_begin(ctx, PROF_START, st, P);
-    if (int0) ctx->int0_sweeps += 1;
-    KT_HIP(launch_spmm_lanczos_start(P, flags | (int0 ? 128 : 0), grid1, M.rowptr, M.col, M.val, n, Z, s0,
-                                     int0 ? reinterpret_cast<double*>(T0) : Xc, part, M.long_rows, M.n_long,
-                                     A->long_thresh, lblocks, st));
-    prof_end(ctx, PROF_START, st);
+    hipStream_t st = L.st;
+    const int grid1 = L.grid1;
+    if (x) {
+        // ys: [1/||x_c|| (P) | 0 (5P) | start pass (g, a, b) = (1, 0, 0) (3P)], from
+        // the device norms (no host round trip)
+        KT_HIP(launch_sweep_scales(dnorms2, ncols, P, 1, ys, nullptr, st));
+        KT_HIP(hipMemsetAsync(V0, 0, L.blk_bytes, st));
+        KT_HIP(launch_weighted_sum(n, 1, P, ncols, x, ldx, 0, ys, V0, P, st));
+        prof_begin(ctx, PROF_YBLOCK, st, P);
+        KT_HIP(launch_spmm_lanczos(P, flags, grid1, M.rowptr, M.col, M.val, n, V0, nullptr, Xc, ys + 6 * P, part,
+                                   M.long_rows, M.n_long, A->long_thresh, L.lblocks, st));
+        prof_end(ctx, PROF_YBLOCK, st);
+    } else {
+        // probes as a packed sign table (n x ceil(P/32) words), gathered by the
+        // start pass instead of an 8nP-byte fp64 block
+        KT_HIP(launch_rademacher_signs(P, n, seed, probe_base, M.perm, Z, st));
+        prof_begin(ctx, PROF_START, st, P);
+        if (int0) ctx->int0_sweeps += 1;
+        KT_HIP(launch_spmm_lanczos_start(P, flags | (int0 ? 128 : 0), grid1, M.rowptr, M.col, M.val, n, Z, s0,
+                                         int0 ? reinterpret_cast<double*>(T0) : Xc, part, M.long_rows, M.n_long,
+                                         A->long_thresh, L.lblocks, st));
+        prof_end(ctx, PROF_START, st);
+    }
     KT_HIP(launch_ycoef(P, part, grid1, 1, !gate && m == 1, s0, ys, rec_at(0, 0), rec_at(1, 0), rec_at(2, 0), guard,
                         st));
 }
 
 void YSweep::step(int j) {
     kt_context_s* ctx = A->ctx;
-    prof_begin(ctx, PROF_SPMM, st, P);
+    hipStream_t st = L.st;
+    const int grid1 = L.grid1, lblocks = L.lblocks, pslot = x ? PROF_YBLOCK : PROF_SPMM;
+    prof_begin(ctx, pslot, st, P);
     // y_{m} is never used: alpha_{m-1} needs only X'A X (the resumable form
     // has no last pass: every row it writes is complete)
     const bool last = !gate && j + 2 == m;
     if (gate) ctx->auto_passes += 1;
+    const double *vc = slot(j), *vo = j > 0 ? slot(j - 1) : nullptr;  // the basis slots (none: nullptr)
+    double* vn = slot(j + 1);
     if (int0 && j == 0) {  // m >= 3: never the last pass; also timed alone in its own slot
         prof_begin(ctx, PROF_FIRST, st, P);
         KT_HIP(launch_spmm_lanczos_first(P, flags, grid1, M.rowptr, M.col, n, T0, s0, Ot, ys + 6 * P, part,
@@ -254,7 +298,7 @@ void YSweep::step(int j) {
         prof_end(ctx, PROF_FIRST, st);
     } else if (last)
         KT_HIP(launch_spmm_quadform(P, flags, grid1, M.rowptr, M.col, M.val, M.lower, n, Xc, ys + 6 * P, part,
-                                    M.long_rows, M.n_long, A->long_thresh, lblocks, st));
+                                    M.long_rows, M.n_long, A->long_thresh, lblocks, st, vc, vo, vn, bcols));
     else if (int0 && j == 1)  // Yold = y_0 from the int16 table
         KT_HIP(launch_spmm_lanczos(P, flags | 128, grid1, M.rowptr, M.col, M.val, n, Xc,
                                    reinterpret_cast<const double*>(T0), Ot, ys + 6 * P, part, M.long_rows,
@@ -262,9 +306,9 @@ void YSweep::step(int j) {
                                    ngate));
     else
         KT_HIP(launch_spmm_lanczos(P, flags, grid1, M.rowptr, M.col, M.val, n, Xc, Yo, Ot, ys + 6 * P, part,
-                                   M.long_rows, M.n_long, A->long_thresh, lblocks, st, nullptr, nullptr, nullptr, 0,
-                                   0.0, gate, ngate));
-    prof_end(ctx, PROF_SPMM, st);
+                                   M.long_rows, M.n_long, A->long_thresh, lblocks, st, vc, vo, vn, bcols, 0.0, gate,
+                                   ngate));
+    prof_end(ctx, pslot, st);
     KT_HIP(launch_ycoef(P, part, grid1, 0, last, 0.0, ys, rec_at(0, j + 1), rec_at(1, j + 1), rec_at(2, j + 1),
                         guard, st, gate, ngate));
     Yo = Xc;  // y_{j+1} overwrites y_{j-1} from the next pass on
@@ -273,119 +317,56 @@ void YSweep::step(int j) {
 }
 
 void YSweep::finish() {
-    KT_HIP(hipMemcpyAsync(rec_host, trec, sizeof(double) * ((size_t)3 * m * P + P), hipMemcpyDeviceToHost, st));
+    KT_HIP(hipMemcpyAsync(rec_host, trec, sizeof(double) * ((size_t)3 * m * P + P), hipMemcpyDeviceToHost, L.st));
 }
 
 void YSweep::finish(int rows) {
     // the three record blocks' first `rows` rows, at the capacity's stride, and the guard
     if (rows > 0)
         KT_HIP(hipMemcpy2DAsync(rec_host, sizeof(double) * (size_t)m * P, trec, sizeof(double) * (size_t)m * P,
-                                sizeof(double) * (size_t)rows * P, 3, hipMemcpyDeviceToHost, st));
-    KT_HIP(hipMemcpyAsync(rec_host + (size_t)3 * m * P, guard, sizeof(double) * P, hipMemcpyDeviceToHost, st));
-}
-
-// y-form sweep seeded by a given device block (the quadrature-only columns
-// of mc_trace's Lanczos Afun, kt_mctrace.cpp): x (n x ldx, ncols columns, in
-// M's row order, squared norms in the device array dnorms2) is normalised into the gathered table
-// v_0 (zero columns stay zero), the pass in start mode forms y_0 = A v_0 with
-// (g, a, b) = (1, 0, 0), then the same passes as the RNG-seeded sweep
-// (steps 0 .. m-2).  rec_host (pinned, or the call waits for the copy)
-// receives [alpha | up | low][m][P] followed by guard[P].  No basis:
-// quadratic forms only.
-YBlockSweep::YBlockSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, const double* x_, int ldx_, int ncols_,
-                         const double* dnorms2_, double* rec_host_, int lane_, double* basis_, int bcols_)
-    : A(A_), M(M_), P(P_), m(m_), x(x_), ldx(ldx_), ncols(ncols_), dnorms2(dnorms2_), rec_host(rec_host_),
-      lane(lane_), basis(basis_), bcols(basis_ ? bcols_ : 0) {
-    kt_context_s* ctx = A->ctx;
-    n = (int)A->n;
-    if (lane < 0 || lane > 3) fail(KT_ERR_ARG, "sweep lane out of range");
-    if (!M.lower) fail(KT_ERR_ARG, "y-form sweep: the CSR copy has no lower-prefix array");
-    if (ncols < 1 || ncols > P) fail(KT_ERR_ARG, "y-form block sweep: 1 <= ncols <= P");
-    if (lane && !ctx->aux_stream[lane - 1])
-        KT_HIP(hipStreamCreateWithFlags(&ctx->aux_stream[lane - 1], hipStreamNonBlocking));
-    st = lane ? ctx->aux_stream[lane - 1] : ctx->stream;
-    grid = spmm_grid(n, P, ctx->num_cu * 4);
-    lblocks = long_blocks_for(M.n_long, ctx->num_cu * 2);
-    grid1 = grid + lblocks;
-    SweepBufs& w = ctx->ws.sweep[lane];
-    blk_bytes = sizeof(double) * (size_t)n * P;
-    w.X0.ensure(blk_bytes);
-    w.X1.ensure(blk_bytes);
-    w.Y.ensure(blk_bytes);
-    w.partial.ensure(sizeof(double) * (size_t)3 * P * grid1);
-    w.coef.ensure(sizeof(double) * 9 * P);
-    w.trec.ensure(sizeof(double) * ((size_t)3 * m * P + P));
-    part = w.partial.as<double>();
-    ys = w.coef.as<double>();
-    trec = w.trec.as<double>();
-    guard = trec + (size_t)3 * m * P;
-    flags = ctx->ky_flags | (A->unit_values ? 2 : 0);
-    if (blk_bytes >= ((size_t)1 << 31)) flags &= ~16;  // sc1 buffer stores take 32-bit offsets
-    V0 = basis ? slot(0) : w.X1.as<double>();  // the start pass's gathered table v_0 (basis slot 0)
-    Xc = w.Y.as<double>();   // y_j
-    Yo = nullptr;            // y_{j-1}
-    Ot = w.X0.as<double>();  // y_{j+1}
-}
-
-void YBlockSweep::start() {
-    // ys: [1/||x_c|| (P) | 0 (5P) | start pass (g, a, b) = (1, 0, 0) (3P)], from
-    // the device norms (no host round trip)
-    KT_HIP(launch_sweep_scales(dnorms2, ncols, P, 1, ys, nullptr, st));
-    KT_HIP(hipMemsetAsync(V0, 0, blk_bytes, st));
-    KT_HIP(launch_weighted_sum(n, 1, P, ncols, x, ldx, 0, ys, V0, P, st));
-    kt_context_s* ctx = A->ctx;
-    prof_begin(ctx, PROF_YBLOCK, st, P);
-    KT_HIP(launch_spmm_lanczos(P, flags, grid1, M.rowptr, M.col, M.val, n, V0, nullptr, Xc, ys + 6 * P, part,
-                               M.long_rows, M.n_long, A->long_thresh, lblocks, st));
-    prof_end(ctx, PROF_YBLOCK, st);
-    KT_HIP(launch_ycoef(P, part, grid1, 1, m == 1, 1.0, ys, rec_at(0, 0), rec_at(1, 0), rec_at(2, 0), guard, st));
-}
-
-void YBlockSweep::step(int j) {
-    const bool last = j + 2 == m;
-    prof_begin(A->ctx, PROF_YBLOCK, st, P);
-    const double* vc = basis ? slot(j) : nullptr;
-    const double* vo = (basis && j > 0) ? slot(j - 1) : nullptr;
-    double* vn = basis ? slot(j + 1) : nullptr;
-    if (last)
-        KT_HIP(launch_spmm_quadform(P, flags, grid1, M.rowptr, M.col, M.val, M.lower, n, Xc, ys + 6 * P, part,
-                                    M.long_rows, M.n_long, A->long_thresh, lblocks, st, vc, vo, vn, bcols));
-    else
-        KT_HIP(launch_spmm_lanczos(P, flags, grid1, M.rowptr, M.col, M.val, n, Xc, Yo, Ot, ys + 6 * P, part,
-                                   M.long_rows, M.n_long, A->long_thresh, lblocks, st, vc, vo, vn, bcols));
-    prof_end(A->ctx, PROF_YBLOCK, st);
-    KT_HIP(launch_ycoef(P, part, grid1, 0, last, 0.0, ys, rec_at(0, j + 1), rec_at(1, j + 1), rec_at(2, j + 1), guard,
-                        st));
-    Yo = Xc;
-    Xc = Ot;
-    Ot = Yo;
-}
-
-void YBlockSweep::finish() {
-    KT_HIP(hipMemcpyAsync(rec_host, trec, sizeof(double) * ((size_t)3 * m * P + P), hipMemcpyDeviceToHost, st));
+                                sizeof(double) * (size_t)rows * P, 3, hipMemcpyDeviceToHost, L.st));
+    KT_HIP(hipMemcpyAsync(rec_host + (size_t)3 * m * P, guard, sizeof(double) * P, hipMemcpyDeviceToHost, L.st));
 }
 
 void lanczos_sweep_y_block(kt_matrix_s* A, const DevCSR& M, int P, int m, const double* x, int ldx, int ncols,
                            const double* dnorms2, double* rec_host, int lane) {
-    YBlockSweep s(A, M, P, m, x, ldx, ncols, dnorms2, rec_host, lane);
-    s.start();
-    for (int j = 0; j + 1 < m; ++j) s.step(j);
-    s.finish();
+    SweepList one;
+    one.emplace_back(new YSweep(A, M, P, m, x, ldx, ncols, dnorms2, rec_host, lane));
+    run_sweeps(one);
 }
 
-// Column c of a sweep record -> symmetric tridiagonal (alpha, off); returns
-// the number of steps before a lucky breakdown (lanczos_krylov.m:91-93).
-int record_tridiag(const double* R, int m, int P, int c, double* al, double* off) {
-    int steps = m;
-    for (int j = 0; j < m; ++j)
-        if (R[(size_t)(2 * m + j) * P + c] < 1e-8) {
+bool guard_tripped(const double* R, int m, int P, int live, const double* n2) {
+    const double* g = R + (size_t)3 * m * P;
+    for (int c = 0; c < live; ++c)
+        if ((!n2 || n2[c] > 0.0) && !(g[c] >= kYformGuard)) return true;
+    return false;
+}
+
+int record_tridiag(const double* R, int mcap, int d, int P, int c, double* al, double* off) {
+    int steps = d;
+    for (int j = 0; j < d; ++j)
+        if (R[(size_t)(2 * mcap + j) * P + c] < 1e-8) {
             steps = j + 1;
             break;
         }
-    for (int j = 0; j < steps; ++j) al[j] = R[(size_t)(0 * m + j) * P + c];
+    for (int j = 0; j < steps; ++j) al[j] = R[(size_t)(0 * mcap + j) * P + c];
     for (int j = 0; j + 1 < steps; ++j)
-        off[j] = 0.5 * (R[(size_t)(2 * m + j) * P + c] + R[(size_t)(1 * m + j + 1) * P + c]);
+        off[j] = 0.5 * (R[(size_t)(2 * mcap + j) * P + c] + R[(size_t)(1 * mcap + j + 1) * P + c]);
     return steps;
+}
+
+void basis_weights(int steps, double nx, const double* fe1, const double* hist, int P, double* W, int ldw) {
+    for (int j = 0; j < steps; ++j) W[(size_t)j * ldw] = hist ? nx * hist[(size_t)j * P] * fe1[j] : nx * fe1[j];
+}
+
+int slq_lanes_env(int dflt) {
+    const char* e = getenv("KT_SLQ_LANES");
+    return e ? atoi(e) : dflt;
+}
+
+bool slq_int0_env() {
+    const char* e = getenv("KT_SLQ_INT0");
+    return !(e && e[0] == '0');
 }
 
 void lanczos_columns(kt_matrix_s* A, const double* X, int ldx, int ncols, int m, int fun,
@@ -511,9 +492,7 @@ void lanczos_columns_split(kt_matrix_s* A, const double* X, int ldx, int ncols, 
     for (size_t i = 0; i < sw.size(); ++i) {
         const Sw& q = sw[i];
         if (used[q.lane]) continue;
-        hipStream_t& as = ctx->aux_stream[q.lane - 1];
-        if (!as) KT_HIP(hipStreamCreateWithFlags(&as, hipStreamNonBlocking));
-        KT_HIP(hipStreamWaitEvent(as, ready, 0));
+        KT_HIP(hipStreamWaitEvent(lane_stream(ctx, q.lane), ready, 0));
         used[q.lane] = true;
     }
     // the explicit sweeps keep their bases (slot j: n x nyc); the basis-forming
@@ -537,16 +516,15 @@ void lanczos_columns_split(kt_matrix_s* A, const double* X, int ldx, int ncols, 
     std::vector<std::vector<int>> by_lane(4);
     for (size_t i = 0; i < sw.size(); ++i) by_lane[sw[i].lane].push_back((int)i);
     for (;;) {
-        std::vector<std::unique_ptr<ExplicitSweep>> ex;
-        std::vector<std::unique_ptr<YBlockSweep>> ybs;
+        SweepList grp, ex;  // the y-form sweeps, then the explicit ones
         for (int l = 0; l < 4; ++l) {
             if (next[l] >= (int)by_lane[l].size()) continue;
             const int i = by_lane[l][next[l]++];
             const Sw& q = sw[i];
             double* R = hr.as<double>() + rec_max * i;
             if (q.yform) {
-                ybs.emplace_back(new YBlockSweep(A, M, q.P, m, Xs + q.c0, ldxs, q.nc, dn2 + q.c0, R, q.lane,
-                                                 q.ybasis ? bases[i].col(0) : nullptr, q.nc));
+                grp.emplace_back(new YSweep(A, M, q.P, m, Xs + q.c0, ldxs, q.nc, dn2 + q.c0, R, q.lane,
+                                            q.ybasis ? bases[i].col(0) : nullptr, q.nc));
             } else {
                 const int nyc = std::max(0, std::min(q.nc, ny - q.c0));
                 ex.emplace_back(new ExplicitSweep(A, M, q.P, m, 0, 0, Xs + q.c0, ldxs, q.nc, dn2 + q.c0, R,
@@ -554,16 +532,9 @@ void lanczos_columns_split(kt_matrix_s* A, const double* X, int ldx, int ncols, 
                                                   nyc));
             }
         }
-        if (ex.empty() && ybs.empty()) break;
-        for (auto& y : ybs) y->start();
-        for (auto& e : ex) e->start();
-        for (int j = 0; j < m; ++j) {
-            for (auto& y : ybs)
-                if (j + 1 < m) y->step(j);
-            for (auto& e : ex) e->step(j);
-        }
-        for (auto& y : ybs) y->finish();
-        for (auto& e : ex) e->finish();
+        for (auto& e : ex) grp.push_back(std::move(e));
+        if (grp.empty()) break;
+        run_sweeps(grp);
     }
     KT_HIP(hipStreamSynchronize(ctx->stream));
     for (int l = 1; l < 4; ++l)
@@ -584,11 +555,8 @@ void lanczos_columns_split(kt_matrix_s* A, const double* X, int ldx, int ncols, 
         const Sw& q = sw[i];
         if (!q.yform) continue;
         double* R = hr.as<double>() + rec_max * i;
-        const double* g = R + (size_t)3 * m * q.P;
-        std::vector<int> bad;
-        for (int c = 0; c < q.nc; ++c)
-            if (norms2[q.c0 + c] > 0.0 && !(g[c] >= kYformGuard)) bad.push_back(c);
-        if (bad.empty()) continue;
+        const double* n2 = norms2.data() + q.c0;
+        if (!guard_tripped(R, m, q.P, q.nc, n2)) continue;
         if (q.ybasis) {
             const int nyc = std::max(0, std::min(q.nc, ny - q.c0));
             DevMat eb;
@@ -604,8 +572,10 @@ void lanczos_columns_split(kt_matrix_s* A, const double* X, int ldx, int ncols, 
         redo.assign((size_t)3 * m * q.P, 0.0);
         lanczos_sweep(A, M, q.P, m, 0, 0, Xs + q.c0, ldxs, q.nc, dn2 + q.c0, redo.data(), nullptr, nullptr, 0);
         KT_HIP(hipStreamSynchronize(ctx->stream));
-        for (int c : bad)
+        for (int c = 0; c < q.nc; ++c) {
+            if (!guard_tripped(R + c, m, q.P, 1, n2 + c)) continue;  // column c alone
             for (int row = 0; row < 3 * m; ++row) R[(size_t)row * q.P + c] = redo[(size_t)row * q.P + c];
+        }
         ctx->yform_redone += 1;
     }
     // per column (one QL pass each, on the host pool): the quadrature and,
@@ -626,7 +596,7 @@ void lanczos_columns_split(kt_matrix_s* A, const double* X, int ldx, int ncols, 
         const Sw& q = sw[i];
         const double* R = hr.as<double>() + rec_max * i;
         std::vector<double> al(m), off(m), fe1(m);
-        const int steps = record_tridiag(R, m, q.P, c, al.data(), off.data());
+        const int steps = record_tridiag(R, m, m, q.P, c, al.data(), off.data());
         if (norms2[q.c0 + c] == 0.0) {
             if (quad) quad[q.c0 + c] = 0.0;
             return;
@@ -637,13 +607,8 @@ void lanczos_columns_split(kt_matrix_s* A, const double* X, int ldx, int ncols, 
         }
         const double qd = tridiag_fun_e1(steps, al.data(), off.data(), fun, fe1.data());
         if (quad) quad[q.c0 + c] = norms2[q.c0 + c] * qd;
-        const double nx = std::sqrt(norms2[q.c0 + c]);
-        if (ex_basis[i]) {
-            for (int j = 0; j < steps; ++j)
-                Ws[i][(size_t)j * nyc + c] = nx * hists[i][(size_t)j * q.P + c] * fe1[j];  // v_j = s_j u_j
-        } else {  // the y-form basis holds the normalised v_j
-            for (int j = 0; j < steps; ++j) Ws[i][(size_t)j * nyc + c] = nx * fe1[j];
-        }
+        basis_weights(steps, std::sqrt(norms2[q.c0 + c]), fe1.data(), ex_basis[i] ? hists[i].data() + c : nullptr, q.P,
+                      Ws[i].data() + c, nyc);
     }, 4);
     for (size_t i = 0; i < sw.size(); ++i) {
         const Sw& q = sw[i];
@@ -661,21 +626,6 @@ void lanczos_columns_split(kt_matrix_s* A, const double* X, int ldx, int ncols, 
         }
     }
     if (perm && ny) KT_HIP(launch_perm_rows((int)n, ny, perm, 0, Ys, ldys, Y, ldy, ctx->stream));
-}
-
-// Column c of a record with row capacity mcap, truncated at depth d: the
-// tridiagonal record_tridiag forms from a d-row record.
-static int record_tridiag_at(const double* R, int mcap, int d, int P, int c, double* al, double* off) {
-    int steps = d;
-    for (int j = 0; j < d; ++j)
-        if (R[(size_t)(2 * mcap + j) * P + c] < 1e-8) {
-            steps = j + 1;
-            break;
-        }
-    for (int j = 0; j < steps; ++j) al[j] = R[(size_t)(0 * mcap + j) * P + c];
-    for (int j = 0; j + 1 < steps; ++j)
-        off[j] = 0.5 * (R[(size_t)(2 * mcap + j) * P + c] + R[(size_t)(1 * mcap + j + 1) * P + c]);
-    return steps;
 }
 
 // The adaptive depth.  Sweeps are always kAdaptP wide, so a
@@ -838,7 +788,7 @@ int lanczos_columns_adaptive(kt_matrix_s* A, const double* X, int ldx, int ncols
         const bool stopped = st[4] != 0.0;
         const int d = stopped ? (int)st[3] : rows[i];
         std::vector<double> al(d), off(d), fe1(d);
-        const int steps = record_tridiag_at(R, m, d, P, c, al.data(), off.data());
+        const int steps = record_tridiag(R, m, d, P, c, al.data(), off.data());
         // unconverged at the cap, unless the record's last row is a lucky breakdown
         cap[t] = !stopped && !(R[(size_t)(2 * m + steps - 1) * P + c] < 1e-8);
         dep[t] = steps;
@@ -848,9 +798,7 @@ int lanczos_columns_adaptive(kt_matrix_s* A, const double* X, int ldx, int ncols
         }
         const double qd = tridiag_fun_e1(steps, al.data(), off.data(), fun, fe1.data());
         if (quad) quad[t] = norms2[t] * qd;
-        const double nx = std::sqrt(norms2[t]);
-        for (int j = 0; j < steps; ++j)
-            Ws[i][(size_t)j * nyc + c] = nx * hists[i][(size_t)j * P + c] * fe1[j];  // v_j = s_j u_j
+        basis_weights(steps, std::sqrt(norms2[t]), fe1.data(), hists[i].data() + c, P, Ws[i].data() + c, nyc);
     }, 4);
     for (int i = 0; i < nsw; ++i) {
         const int nyc = nycs[i], c0 = i * P;
@@ -927,19 +875,15 @@ static int slq_submit(kt_matrix_s* A, int fun, int m, uint64_t seed, int64_t pro
     // overlap another sweep's gather-bound pass; measured best
     // (profiles/r01_yform_lanes.txt): 2 for the y-form pass, 3 for the
     // explicit K1/K2 sweep
-    const char* le = getenv("KT_SLQ_LANES");
-    const int lanes_env = le ? std::max(1, std::min(4, atoi(le))) : (ctx->yform ? 2 : 3);
+    const int lanes_env = std::max(1, std::min(4, slq_lanes_env(ctx->yform ? 2 : 3)));
     pd.lanes = (int)std::max<int64_t>(1, std::min<int64_t>(pd.nsweeps, lanes_env));
-    // KT_SLQ_INT0=0: the y-form sweeps keep y_0 in fp64 (the A/B of the compact form)
-    const char* ie = getenv("KT_SLQ_INT0");
-    const bool int0_env = !(ie && ie[0] == '0');
     if (pd.nsweeps) {
         KT_HIP(hipSetDevice(ctx->device));
         PinnedBuf& hb = w.host_trec[ticket & 1];
         hb.ensure(sizeof(double) * pd.rec * pd.nsweeps);
         double* htrec = hb.as<double>();
         const DevCSR& H = hub_csr(A);
-        const bool int0 = int0_env && int0_applies(A->unit_values, H.max_row, m);
+        const bool int0 = slq_int0_env() && int0_applies(A->unit_values, H.max_row, m);
         // profiling: the previous calls' events are folded in while this
         // call's sweeps run on the device
         prof_recycle(ctx);
@@ -949,26 +893,17 @@ static int slq_submit(kt_matrix_s* A, int fun, int m, uint64_t seed, int64_t pro
         // (launch by launch across the lanes, so every lane starts at once)
         for (int64_t s0 = 0; s0 < pd.nsweeps; s0 += pd.lanes) {
             const int g = (int)std::min<int64_t>(pd.lanes, pd.nsweeps - s0);
-            if (ctx->yform) {
-                std::vector<std::unique_ptr<YSweep>> grp;
-                for (int l = 0; l < g; ++l)
-                    grp.emplace_back(new YSweep(A, H, pd.P, m, seed, probe_offset + (s0 + l) * pd.P,
-                                                htrec + pd.rec * (s0 + l), l, int0));
-                for (auto& y : grp) y->start();
-                for (int j = 0; j + 1 < m; ++j)
-                    for (auto& y : grp) y->step(j);
-                for (auto& y : grp) y->finish();
-            } else {
-                std::vector<std::unique_ptr<ExplicitSweep>> grp;
-                for (int l = 0; l < g; ++l)
-                    grp.emplace_back(new ExplicitSweep(A, H, pd.P, m, seed, probe_offset + (s0 + l) * pd.P, nullptr,
-                                                       0, 0, nullptr, htrec + pd.rec * (s0 + l), nullptr, nullptr,
-                                                       l, 0));
-                for (auto& e : grp) e->start();
-                for (int j = 0; j < m; ++j)
-                    for (auto& e : grp) e->step(j);
-                for (auto& e : grp) e->finish();
+            SweepList grp;
+            for (int l = 0; l < g; ++l) {
+                const int64_t base = probe_offset + (s0 + l) * pd.P;
+                double* R = htrec + pd.rec * (s0 + l);
+                if (ctx->yform)
+                    grp.emplace_back(new YSweep(A, H, pd.P, m, seed, base, R, l, int0));
+                else
+                    grp.emplace_back(
+                        new ExplicitSweep(A, H, pd.P, m, seed, base, nullptr, 0, 0, nullptr, R, nullptr, nullptr, l, 0));
             }
+            run_sweeps(grp);
         }
         for (int l = 0; l < pd.lanes; ++l) {
             if (!pd.done[l]) KT_HIP(hipEventCreateWithFlags(&pd.done[l], hipEventDisableTiming));
@@ -1016,11 +951,8 @@ static void slq_collect(kt_matrix_s* A, int ticket, double* sum_q, double* sum_q
         const DevCSR& H = hub_csr(A);
         int64_t redone = 0;
         for (int64_t sw = 0; sw < pd.nsweeps; ++sw) {
-            const double* g = htrec + rec * sw + (size_t)3 * m * P;
-            const int64_t live = std::min<int64_t>(P, nprobes - sw * P);
-            bool bad = false;
-            for (int64_t c = 0; c < live; ++c) bad |= !(g[c] >= kYformGuard);
-            if (!bad) continue;
+            const int live = (int)std::min<int64_t>(P, nprobes - sw * P);
+            if (!guard_tripped(htrec + rec * sw, m, P, live, nullptr)) continue;
             lanczos_sweep(A, H, P, m, pd.seed, pd.offset + sw * P, nullptr, 0, 0, nullptr, htrec + rec * sw,
                           nullptr, nullptr, 0);
             KT_HIP(hipStreamSynchronize(ctx->stream));
@@ -1036,7 +968,7 @@ static void slq_collect(kt_matrix_s* A, int ticket, double* sum_q, double* sum_q
         std::vector<double> al(m), off(m);
         const int64_t pb = t * chunk, pe = std::min<int64_t>(nprobes, pb + chunk);
         for (int64_t p = pb; p < pe; ++p) {
-            const int steps = record_tridiag(htrec + rec * (p / P), m, P, (int)(p % P), al.data(), off.data());
+            const int steps = record_tridiag(htrec + rec * (p / P), m, m, P, (int)(p % P), al.data(), off.data());
             qv[p] = (double)n * tridiag_quadrature(steps, al.data(), off.data(), fun);
         }
     }, 4);
@@ -1218,14 +1150,11 @@ static void slq_trace_auto(kt_matrix_s* A, int fun, int m_max, double rtol, uint
     // a lane spends about a third of its time in its one-workgroup check, which
     // only other lanes' passes can cover (the bench graph, 1,024 probes:
     // 2.0 / 2.9 / 3.4 / 3.5 evaluations/s at 1 / 2 / 3 / 4 lanes)
-    const char* le = getenv("KT_SLQ_LANES");
-    const int lanes_env = le ? std::max(1, std::min(4, atoi(le))) : 4;
+    const int lanes_env = std::max(1, std::min(4, slq_lanes_env(4)));
     const int lanes = (int)std::max<int64_t>(1, std::min<int64_t>(nsw, lanes_env));
-    const char* ie = getenv("KT_SLQ_INT0");
-    const bool int0_env = !(ie && ie[0] == '0');
     KT_HIP(hipSetDevice(ctx->device));
     const DevCSR& H = hub_csr(A);
-    const bool int0 = int0_env && int0_applies(A->unit_values, H.max_row, hy);
+    const bool int0 = slq_int0_env() && int0_applies(A->unit_values, H.max_row, hy);
     // pinned, per sweep: [record 3 m P | guard P | state P x 8 | guard snapshot P]
     const size_t rec = (size_t)3 * m * P + P, per = rec + (size_t)P * kAdaptState + P;
     w.pin_auto_rec.ensure(sizeof(double) * per * nsw);
@@ -1345,7 +1274,7 @@ static void slq_trace_auto(kt_matrix_s* A, int fun, int m_max, double rtol, uint
             // a column the device did not stop ran every row its sweep wrote
             const bool stopped = st[4] != 0.0;
             const int d = stopped ? (int)st[3] : rows[i];
-            const int steps = record_tridiag_at(R, m, d, P, c, al.data(), off.data());
+            const int steps = record_tridiag(R, m, d, P, c, al.data(), off.data());
             cap[p] = !stopped && !(R[(size_t)(2 * m + steps - 1) * P + c] < 1e-8);
             dep[p] = steps;
             qv[p] = (double)n * tridiag_quadrature(steps, al.data(), off.data(), fun);

@@ -1,6 +1,8 @@
 // kt_slq.h -- probe-Lanczos sweep engine shared by the SLQ hot path and the
 // Lanczos-f Afun of mc_trace.
 #pragma once
+#include <memory>
+
 #include "kt_block.h"
 
 namespace kt {
@@ -16,17 +18,46 @@ void lanczos_sweep(kt_matrix_s* A, const DevCSR& M, int P, int m, uint64_t seed,
                    const double* x, int ldx, int ncols, const double* dnorms2, double* rec_host,
                    DevMat* basis, std::vector<double>* scale_hist, int lane = 0, int bcols = 0);
 
-// lanczos_sweep enqueued step by step: start(), step(j) for j < m, finish().
-// Sweeps on different lanes may be interleaved step by step; two sweeps on
-// one lane may not (they share the lane's buffers).
-class ExplicitSweep {
+// What the sweep classes share on lane `lane`: the lane check, its stream
+// (lane 0: ctx->stream; lane l > 0: ctx->aux_stream[l-1], created on first
+// use by lane_stream), the launch grids of an n x P block and the lane's
+// buffers.
+hipStream_t lane_stream(kt_context_s* ctx, int lane);
+struct SweepLane {
+    SweepLane(kt_matrix_s* A, const DevCSR& M, int P, int lane);
+    hipStream_t st;
+    int grid, lblocks, grid1;  // K2 / short rows, long-row blocks, K1 total
+    size_t blk_bytes;          // one n x P fp64 block
+    SweepBufs& w;
+};
+
+// A sweep enqueued step by step: start(), step(j) for j < nsteps(), finish().
+// run_sweeps queues a list launch by launch -- every start() in list order,
+// then for j = 0, 1, .. step(j) of each sweep with j < nsteps(), then every
+// finish() -- so sweeps on different lanes start at once (the runtime
+// throttles a long enqueue burst to ~58 us per call once the host runs ~1 ms
+// ahead, so a lane queued after a whole sweep would start ms late).  Two
+// sweeps on one lane may not share a list (they share the lane's buffers).
+struct Sweep {
+    virtual ~Sweep() = default;
+    virtual void start() = 0;
+    virtual void step(int j) = 0;
+    virtual void finish() = 0;
+    virtual int nsteps() const = 0;
+};
+using SweepList = std::vector<std::unique_ptr<Sweep>>;
+void run_sweeps(const SweepList& sweeps);
+
+// lanczos_sweep as a Sweep of m steps.
+class ExplicitSweep : public Sweep {
    public:
     ExplicitSweep(kt_matrix_s* A, const DevCSR& M, int P, int m, uint64_t seed, int64_t probe_base, const double* x,
                   int ldx, int ncols, const double* dnorms2, double* rec_host, DevMat* basis,
                   std::vector<double>* scale_hist, int lane, int bcols);
-    void start();
-    void step(int j);
-    void finish();
+    void start() override;
+    void step(int j) override;
+    void finish() override;
+    int nsteps() const override { return m; }
     // The resumable form (lanczos_columns_adaptive): a sweep constructed with
     // capacity m (record rows, scale history, basis slots) runs step(j) only
     // as far as needed; finish(rows) copies the rows written.  The basis of
@@ -37,7 +68,7 @@ class ExplicitSweep {
     void use_basis_chunks(std::vector<DevMat>* chunks, int spc);
     void finish(int rows);
     const double* device_record() const { return trec; }
-    hipStream_t stream() const { return st; }
+    hipStream_t stream() const { return L.st; }
 
    private:
     double* slot(int j);
@@ -54,10 +85,8 @@ class ExplicitSweep {
     double* rec_host;
     DevMat* basis;
     std::vector<double>* scale_hist;
-    int lane, bcols;
-    int n = 0, grid = 0, lblocks = 0, grid1 = 0;
-    size_t blk_bytes = 0;
-    hipStream_t st = nullptr;
+    int bcols, n;
+    SweepLane L;
     double *part1 = nullptr, *part2 = nullptr, *k2s = nullptr, *coef = nullptr, *trec = nullptr, *Yb = nullptr;
     double *ucur = nullptr, *uprev = nullptr, *sc = nullptr, *sp = nullptr, *sn = nullptr, *bbase = nullptr;
     DevBuf* hist_dev = nullptr;
@@ -72,8 +101,9 @@ inline bool int0_applies(bool unit_values, int64_t max_row, int m) {
     return unit_values && max_row <= 32767 && m >= 3;
 }
 
-// lanczos_sweep_y (the RNG-seeded y-form sweep of the Hutchinson hot path)
-// enqueued step by step: start(), step(j) for j < m - 1, finish().
+// The y-form sweep as a Sweep of m - 1 steps, seeded one of two ways.
+// Sign-seeded (the Hutchinson hot path): the probes are a packed sign table
+// from the counter RNG.
 // int0: the compact form -- the start pass stores y_0 as an n x P int16 table
 // behind the sign table, the first step (k_spmm_lanczos_first) gathers it and
 // the second reads it as Yold; from the third step on nothing differs, and
@@ -84,71 +114,53 @@ inline bool int0_applies(bool unit_values, int64_t max_row, int m) {
 // after it and T_{j+2} can be tested; finish(rows) copies the rows written
 // and the guard.  int0 then needs int0_applies at the depth the sweep may
 // reach.  A fixed-depth sweep (gate == nullptr) queues what it always did.
-class YSweep {
+// Block-seeded (lanczos_sweep_y_block): the ncols columns of the device block
+// x.  With `basis` (m slots of n x P, slot j at basis + j n P; bcols > 0) the
+// sweep also forms the normalised Lanczos vectors v_0 .. v_{m-1} of its
+// first bcols columns there (KF_VB passes; v_0 is the start table itself).
+class YSweep : public Sweep {
    public:
     YSweep(kt_matrix_s* A, const DevCSR& M, int P, int m, uint64_t seed, int64_t probe_base, double* rec_host,
            int lane, bool int0 = false, const int* gate = nullptr, int ngate = 0);
-    void start();
-    void step(int j);
-    void finish();
+    YSweep(kt_matrix_s* A, const DevCSR& M, int P, int m, const double* x, int ldx, int ncols, const double* dnorms2,
+           double* rec_host, int lane, double* basis = nullptr, int bcols = 0);
+    void start() override;
+    void step(int j) override;
+    void finish() override;
+    int nsteps() const override { return m - 1; }
     void finish(int rows);
     const double* device_record() const { return trec; }
     const double* device_guard() const { return guard; }
-    hipStream_t stream() const { return st; }
+    hipStream_t stream() const { return L.st; }
 
    private:
+    void setup();
     double* rec_at(int row, int j) { return trec + (size_t)(row * m + j) * P; }
+    double* slot(int j) { return basis ? basis + (size_t)j * n * P : nullptr; }
     kt_matrix_s* A;
     const DevCSR& M;
-    int P, m;
-    uint64_t seed;
-    int64_t probe_base;
+    int P, m, n;
     double* rec_host;
-    int lane;
-    int n = 0, grid = 0, lblocks = 0, grid1 = 0, flags = 0;
-    size_t blk_bytes = 0;
-    hipStream_t st = nullptr;
-    double *part = nullptr, *ys = nullptr, *trec = nullptr, *guard = nullptr;
-    uint32_t* Z = nullptr;
-    double *Xc = nullptr, *Yo = nullptr, *Ot = nullptr;
+    SweepLane L;
+    // the sign seed
+    uint64_t seed = 0;
+    int64_t probe_base = 0;
     bool int0 = false;
-    int16_t* T0 = nullptr;  // int0: y_0's row sums
-    double s0 = 0.0;        // 1 / ||z||
     const int* gate = nullptr;  // the resumable form: the sweep's running words
     int ngate = 0;
-};
-
-// lanczos_sweep_y_block enqueued step by step: start(), step(j) for j < m - 1,
-// finish(); same interleaving rule as ExplicitSweep.
-// With `basis` (m slots of n x P, slot j at basis + j n P; bcols > 0) the
-// sweep also forms the normalised Lanczos vectors v_0 .. v_{m-1} of its
-// first bcols columns there (KF_VB passes; v_0 is the start table itself).
-class YBlockSweep {
-   public:
-    YBlockSweep(kt_matrix_s* A, const DevCSR& M, int P, int m, const double* x, int ldx, int ncols,
-                const double* dnorms2, double* rec_host, int lane, double* basis = nullptr, int bcols = 0);
-    void start();
-    void step(int j);
-    void finish();
-
-   private:
-    double* rec_at(int row, int j) { return trec + (size_t)(row * m + j) * P; }
-    kt_matrix_s* A;
-    const DevCSR& M;
-    int P, m;
-    const double* x;
-    int ldx, ncols;
-    const double* dnorms2;
-    double* rec_host;
-    int lane;
-    int n = 0, grid = 0, lblocks = 0, grid1 = 0, flags = 0;
-    size_t blk_bytes = 0;
-    hipStream_t st = nullptr;
-    double *part = nullptr, *ys = nullptr, *trec = nullptr, *guard = nullptr;
-    double *V0 = nullptr, *Xc = nullptr, *Yo = nullptr, *Ot = nullptr;
+    // the block seed (x != nullptr)
+    const double* x = nullptr;
+    int ldx = 0, ncols = 0;
+    const double* dnorms2 = nullptr;
     double* basis = nullptr;
     int bcols = 0;
-    double* slot(int j) { return basis + (size_t)j * n * P; }
+    int flags = 0;
+    double *part = nullptr, *ys = nullptr, *trec = nullptr, *guard = nullptr;
+    uint32_t* Z = nullptr;   // the sign table
+    int16_t* T0 = nullptr;   // int0: y_0's row sums
+    double* V0 = nullptr;    // the block seed's gathered table v_0 (basis slot 0)
+    double *Xc = nullptr, *Yo = nullptr, *Ot = nullptr;
+    double s0 = 1.0;         // the start's scale: 1 / ||z|| (the block seed is normalised: 1)
 };
 
 // A y-form probe is accepted when every used beta_k^2 kept at least this
@@ -157,7 +169,25 @@ class YBlockSweep {
 // Measured minimum on the golden graphs and Chung-Lu up to m = 100: 6.4e-3.
 constexpr double kYformGuard = 1e-4;
 
-int record_tridiag(const double* R, int m, int P, int c, double* al, double* off);
+// Whether a live column of a y-form record R ([alpha | up | low][m][P], then
+// guard[P]) tripped the guard; n2 (nullable): the columns' squared norms,
+// zero columns never trip.
+bool guard_tripped(const double* R, int m, int P, int live, const double* n2);
+
+// Column c of a sweep record with row capacity mcap, cut at depth d (a
+// fixed-depth record: d == mcap) -> symmetric tridiagonal (alpha, off);
+// returns the number of steps before a lucky breakdown (lanczos_krylov.m:91-93).
+int record_tridiag(const double* R, int mcap, int d, int P, int c, double* al, double* off);
+
+// One f(A) x column's basis weights W[j ldw] = ||x|| fe1_j (j < steps) for a
+// y-form basis (normalised v_j; hist == nullptr), ||x|| hist[j P] fe1_j for an
+// explicit-layout one (v_j = s_j u_j, hist the column's scale history).
+void basis_weights(int steps, double nx, const double* fe1, const double* hist, int P, double* W, int ldw);
+
+// KT_SLQ_LANES (else dflt; the caller clamps to [1, 4]) and KT_SLQ_INT0 (0:
+// the y-form sweeps keep y_0 in fp64, the A/B of the compact form).
+int slq_lanes_env(int dflt);
+bool slq_int0_env();
 
 // For the ncols columns of the device block X (n x ldx, natural row order):
 // quad[c] = x_c' f(A) x_c by m-step Lanczos quadrature (may be NULL) and, if

@@ -419,6 +419,29 @@ int kt_hessianfcn(kt_matrix_t A, int64_t nomega, const double* X, const double* 
  * Perron root of an adjacency matrix). */
 int kt_eigs_leading(kt_matrix_t A, double tol, int maxit, double* lambda, double* v, int* steps);
 
+/* The k largest algebraic eigenpairs of symmetric A, 1 <= k <= 32, k <= n.
+ * lambda (k, descending); V (n x k column-major, original row numbering,
+ * nullable): orthonormal, each column's sign fixed so its sum is >= 0; inside
+ * an eigenspace of a multiple eigenvalue the basis is arbitrary.
+ * resid (k, nullable): ||A v_i - lambda_i v_i||_2 computed explicitly on the
+ * device from the returned vectors, not a Krylov estimate.
+ * Converged: resid_i <= tol * max(|lambda_1|, |lambda_k|); tol <= 0: 1e-10.
+ * max_spmm <= 0: 2000 block products (16 columns each; the residual check of
+ * a restart counts its one or two).  Reaching the cap is not an error:
+ * KT_OK, *nconv (nullable) = how many LEADING pairs converged, resid says
+ * the rest; at least ceil(k / 16) expansions and one check are always made.
+ * spmm (nullable): block products used.  seed keys the start block: column 0
+ * is 1/sqrt(n), columns 1..15 Rademacher from the counter RNG keyed by (seed,
+ * original row index, column).  The same (A, k, tol, max_spmm, seed) gives the
+ * same bits.  Thick-restart block Lanczos (block width 16, basis of 128
+ * columns, full reorthogonalisation, Rayleigh-Ritz on the host); n <= 130
+ * takes the dense host path (spmm = 0).  k outside 1..min(32, n) or a NULL A
+ * or lambda: KT_ERR_ARG before the device is touched; KT_ERR_NOT_HERMITIAN for
+ * non-symmetric A; KT_ERR_ARG while kt_slq_submit calls are outstanding;
+ * KT_ERR_ALLOC if the basis (136 n doubles) does not fit. */
+int kt_eigs_topk(kt_matrix_t A, int k, double tol, int max_spmm, uint64_t seed,
+                 double* lambda, double* V, double* resid, int* nconv, int* spmm);
+
 /* Per-kernel timing (HIP events recorded on the library's stream around each
  * launch of the named kernel while enabled).  kernel: 0 = the probe-Lanczos
  * gather pass (k_spmm_lanczos in the y-form sweep, k_spmm_dot = K1 in the
@@ -434,7 +457,10 @@ int kt_eigs_leading(kt_matrix_t A, double tol, int maxit, double* lambda, double
  * k_diag_finish), 8 = its start-block kernels (k_diag_qtz, k_diag_start; its
  * sweeps' passes report in 3, or 0 and 1 for a sweep redone explicitly),
  * 9 = kt_entries_fun's pair kernels (k_entries_accumulate, k_entries_e0; its
- * sweeps, start blocks and combine report in 3, 8 and 7 as kt_diag_fun's do).
+ * sweeps, start blocks and combine report in 3, 8 and 7 as kt_diag_fun's do),
+ * 10 = kt_eigs_topk's own kernels (k_eig_start, k_eig_rotate, k_eig_resid with
+ * its chunk sum; the solver's block SpMM, Gram and combine launches are the
+ * block-Krylov paths' own and are not event-timed).
  * Returns launch count and summed milliseconds. */
 int kt_profile_enable(kt_context_t ctx, int enable);
 int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* total_ms);
@@ -470,7 +496,8 @@ int kt_debug_delay(kt_context_t ctx, int lane, double microseconds);
  * sums (kt_host_int0_applies; KT_SLQ_INT0=0, read per call, turns the form
  * off), since context creation.  stat 8: y-form step passes queued by
  * kt_slq_trace_auto calls (those queued past a sweep's last stop, which
- * return at once, included), since context creation. */
+ * return at once, included), since context creation.  stat 9: thick restarts
+ * of kt_eigs_topk calls, since context creation. */
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value);
 
 /* Threads of the process-wide host pool (the per-column / per-candidate

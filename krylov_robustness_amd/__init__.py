@@ -10,7 +10,7 @@ interface used by tests and bench.py.
 from ._lib import KrylovError, KrylovLibraryError, FUN_CODES, LIB_PATH
 from .core import (Context, DeviceMatrix, DiagEstimate, EntryEstimate, default_context, device_count, diag_fun,
                    entries_fun, expmv,
-                   eigs_leading, frechet_entries, function_multiple_entries, hessianfcn, hessianfcn_exp,
+                   eigs_leading, eigs_topk, natural_connectivity_topk, frechet_entries, function_multiple_entries, hessianfcn, hessianfcn_exp,
                    hessianfcn_fun, householder_qr,
                    fun_and_grad_krylov_exp, fun_and_grad_krylov_fun, fun_update, lanczos_fmv, lanczos_fmv_auto,
                    mc_trace, normest, slq_collect, slq_plan, slq_quadforms, slq_quadforms_auto, slq_submit, slq_trace,
@@ -31,7 +31,8 @@ __all__ = [
     "mc_trace", "trace_exp", "expmv", "lanczos_fmv", "lanczos_fmv_auto", "trace_fun_update_pairs", "krylov_miobi",
     "greedy_krylov", "find_top_edges", "find_top_missing_edges", "compute_centrality",
     "default_greedy_tol", "krylov_miobi_sharded", "miobi_loop", "select_extreme", "function_multiple_entries", "householder_qr", "frechet_entries",
-    "hessianfcn", "hessianfcn_exp", "hessianfcn_fun", "eigs_leading", "datasets", "matv73",
+    "hessianfcn", "hessianfcn_exp", "hessianfcn_fun", "eigs_leading", "eigs_topk",
+    "natural_connectivity_topk", "datasets", "matv73",
     "load_problem", "load_unweighted", "prepare_unweighted", "prepare_weighted",
     "mc_trace_sharded", "trace_exp_sharded", "edge2low_rank",
 ]

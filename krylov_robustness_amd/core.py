@@ -86,7 +86,7 @@ class Context:
         4 Taylor terms those calls executed, 5 the largest depth the adaptive
         Lanczos Afun used, 6 its columns that reached the depth cap, 7 y-form
         sweeps that carried y_0 as int16 row sums, 8 y-form step passes queued
-        by slq_quadforms_auto."""
+        by slq_quadforms_auto, 9 thick restarts of eigs_topk calls."""
         v = C.c_int64()
         _lib.check(_lib.load().kt_context_stat(self._h, int(which), C.byref(v)))
         return int(v.value)
@@ -321,9 +321,10 @@ def diag_fun(A, nprobes: int, m: int = 30, seed: int = 0, fun="exp", probe_offse
     subgraph centrality of compute_centrality.m:9-10) from the Rademacher
     probes [probe_offset, probe_offset + nprobes) of slq_quadforms' stream.
     deflate: None, an n x k array with orthonormal columns (k <= 16; any
-    orthonormal Q keeps the estimator unbiased), or 1 = the unit leading
-    eigenvector from eigs_leading.  Returns a DiagEstimate."""
-    deflate = _deflate_arg("diag_fun", deflate)
+    orthonormal Q keeps the estimator unbiased), 1 = the unit leading
+    eigenvector from eigs_leading, or k in [2, 16] = the leading k eigenvectors
+    from eigs_topk (A must then be a DeviceMatrix).  Returns a DiagEstimate."""
+    deflate = _deflate_arg("diag_fun", deflate, A)
     D = _dev(A, ctx)
     n, _ = D.info()
     nprobes = int(nprobes)
@@ -365,22 +366,44 @@ class EntryEstimate:
         return np.sqrt(var / (N - 1))
 
 
-def _deflate_arg(who, deflate):
+def _deflate_arg(who, deflate, A=None):
     """deflate of diag_fun / entries_fun checked before a device is touched:
-    None, 1 (the leading eigenvector) or the array."""
-    if isinstance(deflate, (int, np.integer)) and not isinstance(deflate, bool):
-        if int(deflate) not in (0, 1):
-            raise ValueError(f"{who}: deflate as an int supports only 1 (the leading eigenvector); "
-                             "pass an orthonormal n x k array for more")
+    None, an int k in [0, 16] (0: none, 1: the leading eigenvector of
+    eigs_leading, k >= 2: the leading k of eigs_topk) or the array.  With A
+    given, k >= 2 needs A to be a DeviceMatrix: eigs_topk's block solver runs
+    on the device copy, and a host matrix would be uploaded and solved anew on
+    every call -- build D = DeviceMatrix(A) once, or pass the n x k array."""
+    if isinstance(deflate, (bool, np.bool_)):
+        raise ValueError(f"{who}: deflate must be None, an int in [0, 16] or an orthonormal n x k array, "
+                         "not a bool")
+    if isinstance(deflate, (int, np.integer)):
+        if not 0 <= int(deflate) <= 16:
+            raise ValueError(f"{who}: deflate as an int must lie in [0, 16], got {int(deflate)}")
         deflate = int(deflate) or None
+        if deflate is not None and deflate >= 2 and A is not None and not isinstance(A, DeviceMatrix):
+            raise ValueError(f"{who}: deflate={deflate} (the leading eigenvectors of eigs_topk) needs A as a "
+                             "DeviceMatrix; build D = DeviceMatrix(A) once and pass it, or pass an orthonormal "
+                             "n x k array")
     return deflate
 
 
 def _deflation(who, D, n, deflate, ctx):
-    """... and as a column-major n x k block (or None)."""
+    """... and as a column-major n x k block (or None).  An int k >= 2 takes
+    eigs_topk's vectors: orthonormal whether converged or not, so the estimate
+    stays unbiased; fewer than k converged pairs only warn."""
     if deflate is None:
         return None
-    Q = _colmajor(eigs_leading(D, ctx=ctx)[1]) if isinstance(deflate, int) else _colmajor(deflate)
+    if isinstance(deflate, int) and deflate >= 2:
+        _, V, (_, nconv, _) = eigs_topk(D, deflate, ctx=ctx, return_info=True)
+        if nconv < deflate:
+            warnings.warn(f"{who}: eigs_topk converged nconv = {nconv} of the {deflate} deflation vectors; "
+                          "the block is orthonormal and the estimate unbiased, its variance larger",
+                          RuntimeWarning, stacklevel=3)
+        Q = _colmajor(V)
+    elif isinstance(deflate, int):
+        Q = _colmajor(eigs_leading(D, ctx=ctx)[1])
+    else:
+        Q = _colmajor(deflate)
     if Q.shape[0] != n:
         raise ValueError(f"{who}: deflate has {Q.shape[0]} rows, the matrix {n}")
     return Q
@@ -402,7 +425,7 @@ def entries_fun(A, pairs, nprobes: int, m: int = 30, seed: int = 0, fun="exp", p
     n = A.n if isinstance(A, DeviceMatrix) else np.shape(A)[0]
     if P.min() < 0 or P.max() >= n:
         raise ValueError(f"entries_fun: pair indices must lie in [0, {n}) (0-based)")
-    deflate = _deflate_arg("entries_fun", deflate)
+    deflate = _deflate_arg("entries_fun", deflate, A)
     D = _dev(A, ctx)
     n, _ = D.info()
     Q = _deflation("entries_fun", D, n, deflate, ctx)
@@ -771,3 +794,37 @@ def eigs_leading(A, tol=0.0, maxit=0, ctx: Optional[Context] = None):
     _lib.check(_lib.load().kt_eigs_leading(D.handle, float(tol), int(maxit), C.byref(lam), _dptr(v),
                                            C.byref(st)))
     return float(lam.value), v[:n]
+
+
+def eigs_topk(A, k, tol=0.0, max_spmm=0, seed=0, ctx: Optional[Context] = None, return_info=False):
+    """The k largest algebraic eigenpairs of symmetric A on the device
+    (kt_eigs_topk: thick-restart block Lanczos; 1 <= k <= min(32, n)).  Returns
+    (lam, V): lam (k,) descending, V (n, k) orthonormal with column sums >= 0;
+    with return_info also (resid, nconv, spmm) -- resid_i = ||A v_i - lam_i v_i||
+    formed explicitly from the returned vectors, nconv the leading pairs with
+    resid_i <= tol max(|lam_1|, |lam_k|) (tol <= 0: 1e-10), spmm the block
+    products used (max_spmm <= 0: at most 2000; reaching the cap is not an
+    error)."""
+    k = int(k)
+    D = _dev(A, ctx)
+    n, _ = D.info()
+    kk = max(k, 1)
+    lam = np.zeros(kk)
+    V = np.zeros((max(n, 1), kk), order="F")
+    resid = np.zeros(kk)
+    nconv = C.c_int()
+    spmm = C.c_int()
+    _lib.check(_lib.load().kt_eigs_topk(D.handle, k, float(tol), int(max_spmm), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        _dptr(lam), _dptr(V), _dptr(resid), C.byref(nconv), C.byref(spmm)))
+    if return_info:
+        return lam, V[:n], (resid, int(nconv.value), int(spmm.value))
+    return lam, V[:n]
+
+
+def natural_connectivity_topk(A, k, ctx: Optional[Context] = None):
+    """The truncated natural connectivity log(sum_{i <= k} exp(lam_i) / n) from
+    the k largest eigenvalues (eigs_topk), formed as log(sum exp(lam_i - lam_1))
+    + lam_1 - log n."""
+    lam = eigs_topk(A, k, ctx=ctx)[0]
+    n = A.n if isinstance(A, DeviceMatrix) else np.shape(A)[0]
+    return float(np.log(np.sum(np.exp(lam - lam[0]))) + lam[0] - np.log(n))

@@ -138,10 +138,12 @@ struct ProfSlot {
 // the stopping test of an error-controlled SLQ sweep (k_quad_check_wide).
 // PROF_DIAG / PROF_DIAG_START: kt_diag_fun's combine + accumulate kernels and
 // its start-block kernels (kt_diag.hip); kt_entries_fun's sweeps report in the
-// same two.  PROF_ENTRIES: its pair kernels (k_entries_accumulate, k_entries_e0)
+// same two.  PROF_ENTRIES: its pair kernels (k_entries_accumulate, k_entries_e0).
+// PROF_EIGS: kt_eigs_topk's own kernels (k_eig_start, k_eig_rotate, k_eig_resid)
 enum {
     PROF_SPMM = 0, PROF_UPDATE = 1, PROF_START = 2, PROF_YBLOCK = 3, PROF_EXPMV = 4, PROF_FIRST = 5,
-    PROF_CHECK = 6, PROF_DIAG = 7, PROF_DIAG_START = 8, PROF_ENTRIES = 9, PROF_NSLOTS = 10
+    PROF_CHECK = 6, PROF_DIAG = 7, PROF_DIAG_START = 8, PROF_ENTRIES = 9, PROF_EIGS = 10,
+    PROF_NSLOTS = 11
 };
 
 // Buffers of one probe-sweep lane (kt_slq.cpp); two lanes let two sweeps
@@ -258,6 +260,7 @@ struct kt_context_s {
     int64_t adapt_capped = 0;     // ... and its columns that reached the depth cap unconverged
     int64_t int0_sweeps = 0;      // y-form sweeps that carried y_0 as int16 row sums (kt_slq.h int0_applies)
     int64_t auto_passes = 0;      // y-form step passes queued by kt_slq_trace_auto calls (gated ones included)
+    int64_t eigs_restarts = 0;    // thick restarts of kt_eigs_topk calls
     int ky_flags = 8;   // y-form pass flags (8 = nontemporal store of y_{j+1}, +0.3 %)
     bool yform = true;  // KT_SLQ_YFORM=0: the hot path runs the explicit K1/K2 sweep
     void* blas = nullptr;  // rocblas_handle, created on first block-Krylov use

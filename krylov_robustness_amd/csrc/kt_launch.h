@@ -225,6 +225,21 @@ hipError_t launch_entries_accumulate(int P, int KP, int64_t npairs, const void* 
                                      double* esum2, hipStream_t st);
 hipError_t launch_entries_e0(int64_t npairs, const void* tab, int k, const double* Q, const double* G, int ld,
                              const double* H, double* e0, hipStream_t st);
+// kt_eigs_topk's streaming kernels (kt_eigs.hip; driver kt_eigs.cpp).
+// launch_eig_start: the columns c < 16 of X (n x ldx row-major) whose bit is set
+// in mask become the counter-RNG Rademacher column col0 + c keyed by (seed,
+// ORIGINAL row perm[r], col0 + c) (perm nullptr: identity); ones_first: column
+// 0 is 1 / sqrt(n) instead.
+hipError_t launch_eig_start(int64_t n, uint64_t seed, int64_t col0, unsigned mask, bool ones_first, const int* perm,
+                            double* X, int ldx, hipStream_t st);
+// V(:, 0:p) <- V(:, 0:mb) Y in place (Y: mb x p ROW-major, device); mb even
+// <= 128, p in {16, 32, 48}, p <= mb <= ld
+hipError_t launch_eig_rotate(int64_t n, int mb, int p, double* V, int ld, const double* Y, hipStream_t st);
+// out[0:kp] = ||AX_i - theta_i X_i||^2, out[kp:2kp] = ||X_i||^2, out[2kp:3kp] =
+// sum_r X_i(r); kp = 16 or 32; part: 3 kp eig_resid_chunks(n) doubles
+int eig_resid_chunks(int64_t n);
+hipError_t launch_eig_resid(int64_t n, int kp, const double* X, int ldx, const double* AX, int ldax,
+                            const double* theta, double* part, double* out, hipStream_t st);
 int inf_norm_blocks();
 // normest1 (t = 1) reductions, normest1_blocks(n) partials each: sum |Y| in
 // partial[0, nb), S_prev . S in partial[nb, 2 nb), S = mysign(Y); per-block

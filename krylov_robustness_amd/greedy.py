@@ -206,7 +206,8 @@ def find_top_edges_fun(A, num, fun="exp", nprobes=256, deflate=1, m=30, seed=0, 
     derivative; for a general f pass its derivative's code as `fun` (sinh to
     rank for cosh and the reverse).  Missing edges are O(n^2): score a
     candidate list of them with entries_fun."""
-    from .core import entries_fun
+    from .core import _deflate_arg, entries_fun
+    deflate = _deflate_arg("find_top_edges_fun", deflate, A)
     D = _dev(A, ctx)
     I, J = _tril_edges(D.to_scipy())
     if len(I) < num:
@@ -293,14 +294,16 @@ def compute_centrality(A, kind="eig", ctx: Optional[Context] = None, **kw):
     'deg' = column sums (:18-19); 'exp' = diag(expm(A)), the subgraph
     centrality (:9-10): the dense expm for a host matrix, as the reference,
     and for a DeviceMatrix the deflated stochastic estimate diag_fun(A,
-    nprobes=256, deflate=1).mean (kw: nprobes, deflate, m, seed, block)."""
+    nprobes=256, deflate=1).mean (kw: nprobes, deflate, m, seed, block;
+    deflate = k in [2, 16] deflates the leading k eigenvectors of eigs_topk)."""
     import scipy.sparse as sp
     import scipy.sparse.linalg as sla
     if isinstance(A, DeviceMatrix):
         if kind == "deg":
             return np.asarray(A.to_scipy().sum(axis=0)).ravel()
         if kind == "exp":
-            from .core import diag_fun
+            from .core import _deflate_arg, diag_fun
+            _deflate_arg("compute_centrality", kw.get("deflate", 1))
             return diag_fun(A, kw.get("nprobes", 256), m=kw.get("m", 30), seed=kw.get("seed", 0),
                             block=kw.get("block", 0), deflate=kw.get("deflate", 1), ctx=ctx).mean
         from .core import eigs_leading

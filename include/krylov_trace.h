@@ -442,6 +442,45 @@ int kt_eigs_leading(kt_matrix_t A, double tol, int maxit, double* lambda, double
 int kt_eigs_topk(kt_matrix_t A, int k, double tol, int max_spmm, uint64_t seed,
                  double* lambda, double* V, double* resid, int* nconv, int* spmm);
 
+/* The MIOBI edge score from t eigenpairs on a pair list (MIOBIBreakEdge2.m:60-68):
+ * score[p] = sum_{k < t} exp(lambda[k]) exp(sign V[pi[p], k] V[pj[p], k]),
+ * sign = -2 for removing the pair's edge, +2 for adding it.  lambda (t), V
+ * (n x t column-major), pi / pj (npairs, 0-based) and score (npairs) are host
+ * arrays; 1 <= t <= 32.  The t terms are added in a fixed order: the same
+ * arguments give the same bits.  NULL arguments, t or an index out of range:
+ * KT_ERR_ARG before the device is touched. */
+int kt_pairs_score_topk(kt_context_t ctx, int64_t n, int t, const double* lambda, const double* V,
+                        int64_t npairs, const int64_t* pi, const int64_t* pj, double sign, double* score);
+
+/* MIOBI's top-t edge removal (MIOBIBreakEdge2.m, MIOBIBreakEdge2_weighted.m)
+ * with the step loop on the device: k times, score every remaining edge of
+ * the upper triangle with the leading t eigenpairs (kt_eigs_topk with tol,
+ * max_spmm, seed; column 0 of V taken by absolute value), remove the edge with
+ * the smallest score (exactly equal scores: the smaller (max(i, j), min(i, j)),
+ * the order of find(triu(A, 1))), and shift the eigenvalues to first order,
+ * lambda_k += -2 a_ij V[i, k] V[j, k].  mode 0 (`reference`): V stays as
+ * computed, which is what the reference's update amounts to;
+ * mode 1 (`paper`): V <- V (I + S), S(r, c) = dH(r, c) / (lambda_c - lambda_r)
+ * for r != c (0 where the denominator is 0 or |lambda_c - lambda_r| <= gap_rel
+ * |lambda_1|), columns normalised, column 0 by absolute value.  refresh > 0:
+ * after every refresh-th step but the last the removals so far are applied to
+ * A and the eigenpairs are recomputed; refresh <= 0: never.  The steps between
+ * two recomputations are queued without a host synchronisation.  A is edited
+ * in place (the selected edges removed).
+ * Outputs: sel_i >= sel_j (0-based) and sel_score, k each; lambda_track
+ * (nullable), (k + 1) x t ROW-major: row s = the eigenvalues that score step
+ * s + 1 (row 0 the computed ones, a recomputation replaces its step's row);
+ * V_final (nullable), n x t column-major: V after the last step; *nsel < k
+ * when no edge was left; *nconv_min (nullable) the smallest nconv a
+ * kt_eigs_topk run returned (an unconverged pair is reported, not an error);
+ * *refreshes (nullable) the recomputations.  The same arguments give the same
+ * bits.  KT_ERR_ARG before the device is touched for NULL arguments, k < 0, t
+ * outside 2..min(32, n), a mode other than 0 / 1 or a negative gap_rel;
+ * KT_ERR_NOT_HERMITIAN for non-symmetric A. */
+int kt_miobi_break(kt_matrix_t A, int k, int t, int refresh, int mode, double gap_rel, double tol,
+                   int max_spmm, uint64_t seed, int64_t* sel_i, int64_t* sel_j, double* sel_score,
+                   double* lambda_track, double* V_final, int64_t* nsel, int* nconv_min, int* refreshes);
+
 /* Per-kernel timing (HIP events recorded on the library's stream around each
  * launch of the named kernel while enabled).  kernel: 0 = the probe-Lanczos
  * gather pass (k_spmm_lanczos in the y-form sweep, k_spmm_dot = K1 in the
@@ -460,7 +499,10 @@ int kt_eigs_topk(kt_matrix_t A, int k, double tol, int max_spmm, uint64_t seed,
  * sweeps, start blocks and combine report in 3, 8 and 7 as kt_diag_fun's do),
  * 10 = kt_eigs_topk's own kernels (k_eig_start, k_eig_rotate, k_eig_resid with
  * its chunk sum; the solver's block SpMM, Gram and combine launches are the
- * block-Krylov paths' own and are not event-timed).
+ * block-Krylov paths' own and are not event-timed),
+ * 11 = kt_miobi_break's steps, one interval per step (k_miobi_score,
+ * k_miobi_pick and, in mode 1, the rotation and normalisation), and
+ * kt_pairs_score_topk's scoring launch.
  * Returns launch count and summed milliseconds. */
 int kt_profile_enable(kt_context_t ctx, int enable);
 int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* total_ms);

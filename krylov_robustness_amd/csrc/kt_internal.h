@@ -140,10 +140,13 @@ struct ProfSlot {
 // its start-block kernels (kt_diag.hip); kt_entries_fun's sweeps report in the
 // same two.  PROF_ENTRIES: its pair kernels (k_entries_accumulate, k_entries_e0).
 // PROF_EIGS: kt_eigs_topk's own kernels (k_eig_start, k_eig_rotate, k_eig_resid)
+// PROF_MIOBI: one interval per kt_miobi_break step (k_miobi_score, k_miobi_pick
+// and, in `paper` mode, the rotation and normalisation) and per
+// kt_pairs_score_topk scoring launch
 enum {
     PROF_SPMM = 0, PROF_UPDATE = 1, PROF_START = 2, PROF_YBLOCK = 3, PROF_EXPMV = 4, PROF_FIRST = 5,
-    PROF_CHECK = 6, PROF_DIAG = 7, PROF_DIAG_START = 8, PROF_ENTRIES = 9, PROF_EIGS = 10,
-    PROF_NSLOTS = 11
+    PROF_CHECK = 6, PROF_DIAG = 7, PROF_DIAG_START = 8, PROF_ENTRIES = 9, PROF_EIGS = 10, PROF_MIOBI = 11,
+    PROF_NSLOTS = 12
 };
 
 // Buffers of one probe-sweep lane (kt_slq.cpp); two lanes let two sweeps

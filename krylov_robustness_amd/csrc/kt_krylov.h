@@ -30,4 +30,9 @@ kt_matrix_s* twin_of(kt_matrix_s* A);
 // sparse assignment does) on the host copy and refresh the device copies.
 void set_pairs(kt_matrix_s* A, int64_t count, const int64_t* ei, const int64_t* ej, double value);
 
+// kt_eigs_topk past its argument checks (kt_eigs.cpp): the k <= min(32, n)
+// largest eigenpairs of symmetric A; V (nullable) host n x k column-major
+void eigs_topk_impl(kt_matrix_s* A, int k, double tol, int max_spmm, uint64_t seed, double* lambda, double* V,
+                    double* resid, int* nconv, int* spmm_out);
+
 }  // namespace kt

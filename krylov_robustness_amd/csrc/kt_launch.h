@@ -240,6 +240,32 @@ hipError_t launch_eig_rotate(int64_t n, int mb, int p, double* V, int ld, const 
 int eig_resid_chunks(int64_t n);
 hipError_t launch_eig_resid(int64_t n, int kp, const double* X, int ldx, const double* AX, int ldax,
                             const double* theta, double* part, double* out, hipStream_t st);
+// MIOBI top-t edge scores and the device step (kt_miobi.hip; driver
+// kt_miobi.cpp).  V: n x kMiobiLd row-major in ORIGINAL numbering, columns >= t
+// zero; c[k] = exp(e[k]); pairs (pi, pj) 0-based with an optional alive byte.
+// launch_miobi_score: nblocks = miobi_score_blocks(npairs, max_blocks)
+// workgroups, each leaving its first candidate (smallest score, ties by the
+// key (max, min), then by list index; index -1: none) in part_*[b]; score
+// (nullable) receives every live pair's score.  launch_miobi_pick reduces the
+// candidates and applies the step (see the kernel); state = {steps, stop}.
+// launch_miobi_normalise: V's columns to unit 2-norm, column 0 non-negative
+// (part: kMiobiLd miobi_norm_blocks(n) doubles).  A set state[1] / *stop makes
+// each of the three a no-op.
+constexpr int kMiobiLd = 32;
+constexpr int kMiobiTilePairs = 64;   // pairs a workgroup scores per trip
+constexpr int kMiobiMaxBlocks = 2048;
+int miobi_score_blocks(int64_t npairs, int max_blocks);
+hipError_t launch_miobi_setc(int t, const double* e, double* c, hipStream_t st);
+hipError_t launch_miobi_score(int64_t npairs, int t, const double* V, const double* c, const int* pi, const int* pj,
+                              const unsigned char* alive, double sign, double* score, int nblocks, double* part_s,
+                              unsigned long long* part_key, int* part_idx, const int* stop, hipStream_t st);
+hipError_t launch_miobi_pick(int nparts, const double* part_s, const unsigned long long* part_key,
+                             const int* part_idx, int t, int paper, double gap_rel, const double* V, double* e,
+                             double* c, const int* pi, const int* pj, const double* wt, unsigned char* alive,
+                             int* sel_i, int* sel_j, double* sel_score, double* track, double* M, int* state,
+                             hipStream_t st);
+int miobi_norm_blocks(int64_t n);
+hipError_t launch_miobi_normalise(int64_t n, double* V, double* part, const int* state, hipStream_t st);
 int inf_norm_blocks();
 // normest1 (t = 1) reductions, normest1_blocks(n) partials each: sum |Y| in
 // partial[0, nb), S_prev . S in partial[nb, 2 nb), S = mysign(Y); per-block

@@ -1,0 +1,327 @@
+// kt_miobi.hip -- the kernels of kt_miobi_break and kt_pairs_score_topk
+// (kt_miobi.cpp): the MIOBI edge score from the top-t
+// eigenpairs on a pair list, the global argmin with the step applied on the
+// device, and the column normalisation of the `paper` eigenvector update.
+//
+// V is n x 32 row-major in ORIGINAL numbering (t <= 32 live columns, the rest
+// zero): one row is 256 bytes, so a half-wave with lane = column reads a row
+// in one coalesced access.  No atomics; every sum has a fixed order, and the
+// argmin is the minimum of a total order (score, key, list index), so neither
+// depends on the grid or on how the pair list is stored.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "kt_launch.h"
+#include "kt_wave.h"
+
+namespace kt {
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int kLd = kMiobiLd;
+constexpr int kHalves = 8;                        // half-waves of a 256-thread workgroup
+constexpr int kPer = kMiobiTilePairs / kHalves;   // pairs a half-wave has in flight per tile
+
+// (s1, k1, i1) before (s2, k2, i2): the smaller score, exactly equal scores by
+// the smaller key (max(i, j), min(i, j)) -- MATLAB's find(triu(A, 1)) order --
+// then by the smaller list index (a list may name a pair twice).  i < 0: no
+// candidate.  A NaN score loses to every number.
+__device__ __forceinline__ bool before(double s1, u64 k1, int i1, double s2, u64 k2, int i2) {
+    if (i1 < 0) return false;
+    if (i2 < 0) return true;
+    if (s1 != s2) return s1 < s2 || (s2 != s2 && s1 == s1);
+    if (k1 != k2) return k1 < k2;
+    return i1 < i2;
+}
+
+__device__ __forceinline__ u64 pair_key(int i, int j) {
+    const unsigned hi = (unsigned)max(i, j), lo = (unsigned)min(i, j);
+    return ((u64)hi << 32) | lo;
+}
+
+}  // namespace
+
+// c[k] = exp(e[k]) for k < t, 0 for t <= k < 32
+__global__ __launch_bounds__(64) void k_miobi_setc(int t, const double* __restrict__ e, double* __restrict__ c) {
+    const int k = threadIdx.x;
+    if (k < kLd) c[k] = k < t ? exp(e[k]) : 0.0;
+}
+
+hipError_t launch_miobi_setc(int t, const double* e, double* c, hipStream_t st) {
+    if (t < 1 || t > kLd) return hipErrorInvalidValue;
+    k_miobi_setc<<<1, 64, 0, st>>>(t, e, c);
+    return hipGetLastError();
+}
+
+// score[p] = sum_{k < t} c[k] exp(sign V[pi[p], k] V[pj[p], k]) for the pairs
+// whose alive byte is set (alive nullptr: all).  One half-wave per pair, lane =
+// k; a workgroup takes tiles of 64 pairs, each half-wave kPer of them with all
+// 2 kPer row reads issued before the first exp.  The t terms are added by the
+// xor butterfly 16, 8, 4, 2, 1 (kt_wave.h), called by every lane of the wave
+// whatever its pair: the order is fixed, the same inputs give the same bits.
+// score (nullable) receives the live pairs' scores; part_*[blockIdx.x] the
+// workgroup's first candidate in the order of before().  stop (nullable): a
+// set word makes the launch a no-op.
+__global__ __launch_bounds__(256) void k_miobi_score(int64_t npairs, int t, const double* __restrict__ V,
+                                                     const double* __restrict__ c, const int* __restrict__ pi,
+                                                     const int* __restrict__ pj,
+                                                     const unsigned char* __restrict__ alive, double sign,
+                                                     double* __restrict__ score, double* __restrict__ part_s,
+                                                     u64* __restrict__ part_key, int* __restrict__ part_idx,
+                                                     const int* __restrict__ stop) {
+    if (stop && *stop) return;  // the same word for every thread
+    __shared__ double red_s[kHalves];
+    __shared__ u64 red_k[kHalves];
+    __shared__ int red_i[kHalves];
+    const int k = threadIdx.x & 31, h = threadIdx.x >> 5;
+    const double ck = k < t ? c[k] : 0.0;
+    double bs = 0.0;
+    u64 bk = 0;
+    int bi = -1;
+    const int64_t ntiles = (npairs + kMiobiTilePairs - 1) / kMiobiTilePairs;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // wave-uniform trip count
+        double a[kPer], b[kPer];
+        int ii[kPer], jj[kPer];
+        bool ok[kPer];
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) {
+            const int64_t p = tile * kMiobiTilePairs + u * kHalves + h;
+            ok[u] = p < npairs && (!alive || alive[p]);
+            ii[u] = jj[u] = 0;
+            a[u] = b[u] = 0.0;
+            if (ok[u]) {
+                ii[u] = pi[p];
+                jj[u] = pj[p];
+                a[u] = V[(int64_t)ii[u] * kLd + k];
+                b[u] = V[(int64_t)jj[u] * kLd + k];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kPer; ++u) {
+            double s = k < t ? ck * exp(sign * (a[u] * b[u])) : 0.0;
+            s += shfl_xor_d(s, 16);
+            s += shfl_xor_d(s, 8);
+            s += shfl_xor_d(s, 4);
+            s += shfl_xor_d(s, 2);
+            s += shfl_xor_d(s, 1);
+            if (ok[u]) {
+                const int p = (int)(tile * kMiobiTilePairs + u * kHalves + h);
+                if (score && k == 0) score[p] = s;
+                const u64 key = pair_key(ii[u], jj[u]);
+                if (before(s, key, p, bs, bk, bi)) {
+                    bs = s;
+                    bk = key;
+                    bi = p;
+                }
+            }
+        }
+    }
+    if (k == 0) {
+        red_s[h] = bs;
+        red_k[h] = bk;
+        red_i[h] = bi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < kHalves; ++q)
+            if (before(red_s[q], red_k[q], red_i[q], bs, bk, bi)) {
+                bs = red_s[q];
+                bk = red_k[q];
+                bi = red_i[q];
+            }
+        part_s[blockIdx.x] = bs;
+        part_key[blockIdx.x] = bk;
+        part_idx[blockIdx.x] = bi;
+    }
+}
+
+int miobi_score_blocks(int64_t npairs, int max_blocks) {
+    const int64_t ntiles = (npairs + kMiobiTilePairs - 1) / kMiobiTilePairs;
+    const int cap = max_blocks > 0 ? std::min(max_blocks, kMiobiMaxBlocks) : kMiobiMaxBlocks;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, cap));
+}
+
+hipError_t launch_miobi_score(int64_t npairs, int t, const double* V, const double* c, const int* pi, const int* pj,
+                              const unsigned char* alive, double sign, double* score, int nblocks, double* part_s,
+                              unsigned long long* part_key, int* part_idx, const int* stop, hipStream_t st) {
+    if (npairs < 0 || npairs > INT32_MAX || t < 1 || t > kLd || nblocks < 1 || nblocks > kMiobiMaxBlocks)
+        return hipErrorInvalidValue;
+    k_miobi_score<<<nblocks, 256, 0, st>>>(npairs, t, V, c, pi, pj, alive, sign, score, part_s, part_key, part_idx,
+                                           stop);
+    return hipGetLastError();
+}
+
+// One workgroup: the minimum of the nparts workgroup candidates in the order
+// of before(), then the step (MIOBIBreakEdge2.m:71-90, :140): with (i, j) the
+// pair, a its weight (wt nullptr: 1) and s = state[0] the steps so far,
+//   sel_i[s] = max(i, j), sel_j[s] = min(i, j), sel_score[s] = its score,
+//   alive[pair] = 0, e[k] += -2 a V[i, k] V[j, k], c[k] = exp(e[k]),
+//   track[(s + 1) 32 + k] = e[k]  (k < t),  state[0] = s + 1.
+// paper != 0 also writes M (32 x 32 row-major) = I + S with S(r, c) =
+// dH(r, c) / (e_c - e_r) for r != c < t, dH = -a (V[i, r] V[j, c] + V[j, r]
+// V[i, c]), from e BEFORE the shift (:95-102, deltaV = V innerSum); 0 where the
+// denominator is 0 or |e_c - e_r| <= gap_rel |e_0|; rows and columns >= t zero.
+// No live candidate: state[1] = 1 (and M = I) and nothing else; a launch that
+// finds state[1] set returns at once.
+__global__ __launch_bounds__(256) void k_miobi_pick(int nparts, const double* __restrict__ part_s,
+                                                    const u64* __restrict__ part_key,
+                                                    const int* __restrict__ part_idx, int t, int paper,
+                                                    double gap_rel, const double* __restrict__ V,
+                                                    double* __restrict__ e, double* __restrict__ c,
+                                                    const int* __restrict__ pi, const int* __restrict__ pj,
+                                                    const double* __restrict__ wt, unsigned char* __restrict__ alive,
+                                                    int* __restrict__ sel_i, int* __restrict__ sel_j,
+                                                    double* __restrict__ sel_score, double* __restrict__ track,
+                                                    double* __restrict__ M, int* __restrict__ state) {
+    if (state[1]) return;
+    __shared__ double ss[256];
+    __shared__ u64 sk[256];
+    __shared__ int si[256];
+    __shared__ double su[kLd], sv[kLd], se[kLd];
+    const int tid = threadIdx.x;
+    const int step = state[0];
+    double bs = 0.0;
+    u64 bk = 0;
+    int bi = -1;
+    for (int q = tid; q < nparts; q += 256)
+        if (before(part_s[q], part_key[q], part_idx[q], bs, bk, bi)) {
+            bs = part_s[q];
+            bk = part_key[q];
+            bi = part_idx[q];
+        }
+    ss[tid] = bs;
+    sk[tid] = bk;
+    si[tid] = bi;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w && before(ss[tid + w], sk[tid + w], si[tid + w], ss[tid], sk[tid], si[tid])) {
+            ss[tid] = ss[tid + w];
+            sk[tid] = sk[tid + w];
+            si[tid] = si[tid + w];
+        }
+        __syncthreads();
+    }
+    const int idx = si[0];
+    if (idx < 0) {
+        if (tid == 0) state[1] = 1;
+        if (paper)
+            for (int q = tid; q < kLd * kLd; q += 256) M[q] = (q >> 5) == (q & 31) && (q & 31) < t ? 1.0 : 0.0;
+        return;
+    }
+    const int i = pi[idx], j = pj[idx];
+    const double a = wt ? wt[idx] : 1.0;
+    if (tid < kLd) {
+        const double u = tid < t ? V[(int64_t)i * kLd + tid] : 0.0;
+        const double v = tid < t ? V[(int64_t)j * kLd + tid] : 0.0;
+        const double eo = tid < t ? e[tid] : 0.0;
+        su[tid] = u;
+        sv[tid] = v;
+        se[tid] = eo;
+        if (tid < t) {
+            const double en = eo + (-2.0 * a) * (u * v);
+            e[tid] = en;
+            c[tid] = exp(en);
+            track[(int64_t)(step + 1) * kLd + tid] = en;
+        }
+    }
+    if (tid == 0) {
+        sel_i[step] = max(i, j);
+        sel_j[step] = min(i, j);
+        sel_score[step] = ss[0];
+        alive[idx] = 0;
+    }
+    __syncthreads();  // every thread has read state[0]; su / sv / se are complete
+    if (tid == 0) state[0] = step + 1;
+    if (paper) {
+        const double floor_gap = gap_rel * fabs(se[0]);
+        for (int q = tid; q < kLd * kLd; q += 256) {
+            const int r = q >> 5, cc = q & 31;
+            double m = 0.0;
+            if (r < t && cc < t) {
+                if (r == cc) {
+                    m = 1.0;
+                } else {
+                    const double d = se[cc] - se[r];
+                    const double dh = -a * (su[r] * sv[cc] + sv[r] * su[cc]);
+                    m = (d == 0.0 || fabs(d) <= floor_gap) ? 0.0 : dh / d;
+                }
+            }
+            M[q] = m;
+        }
+    }
+}
+
+hipError_t launch_miobi_pick(int nparts, const double* part_s, const unsigned long long* part_key,
+                             const int* part_idx, int t, int paper, double gap_rel, const double* V, double* e,
+                             double* c, const int* pi, const int* pj, const double* wt, unsigned char* alive,
+                             int* sel_i, int* sel_j, double* sel_score, double* track, double* M, int* state,
+                             hipStream_t st) {
+    if (nparts < 1 || nparts > kMiobiMaxBlocks || t < 1 || t > kLd || (paper && !M)) return hipErrorInvalidValue;
+    k_miobi_pick<<<1, 256, 0, st>>>(nparts, part_s, part_key, part_idx, t, paper, gap_rel, V, e, c, pi, pj, wt, alive,
+                                    sel_i, sel_j, sel_score, track, M, state);
+    return hipGetLastError();
+}
+
+// The `paper` update's normalisation (MIOBIBreakEdge2.m:136-142): every column
+// of V divided by its 2-norm, column 0 made non-negative.  k_miobi_colsq:
+// workgroup b adds the squares of rows 8 b + (tid >> 5) + 8 gridDim.x q, q
+// ascending, per thread, then the eight row groups in ascending order.
+// k_miobi_scale adds the workgroups' partials in ascending order (every
+// workgroup the same sum) and scales its rows; a zero column stays zero.
+// Both return at once when state[1] is set.
+__global__ __launch_bounds__(256) void k_miobi_colsq(int64_t n, const double* __restrict__ V,
+                                                     double* __restrict__ part, const int* __restrict__ state) {
+    if (state[1]) return;
+    __shared__ double red[256];
+    const int k = threadIdx.x & 31, g = threadIdx.x >> 5;
+    double acc = 0.0;
+    for (int64_t r = (int64_t)blockIdx.x * 8 + g; r < n; r += (int64_t)gridDim.x * 8) {
+        const double x = V[r * kLd + k];
+        acc = fma(x, x, acc);
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x < kLd) {
+        double s = 0.0;
+        for (int q = 0; q < 8; ++q) s += red[q * 32 + threadIdx.x];
+        part[(size_t)blockIdx.x * kLd + threadIdx.x] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_miobi_scale(int64_t n, int nparts, double* __restrict__ V,
+                                                     const double* __restrict__ part,
+                                                     const int* __restrict__ state) {
+    if (state[1]) return;
+    __shared__ double inv[kLd];
+    if (threadIdx.x < kLd) {
+        double s = 0.0;
+        for (int q = 0; q < nparts; ++q) s += part[(size_t)q * kLd + threadIdx.x];
+        inv[threadIdx.x] = s > 0.0 ? 1.0 / sqrt(s) : 0.0;
+    }
+    __syncthreads();
+    const int k = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const double f = inv[k];
+    for (int64_t r = (int64_t)blockIdx.x * 8 + g; r < n; r += (int64_t)gridDim.x * 8) {
+        const double x = V[r * kLd + k] * f;
+        V[r * kLd + k] = k == 0 ? fabs(x) : x;
+    }
+}
+
+int miobi_norm_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 63) / 64, 256)); }
+
+hipError_t launch_miobi_normalise(int64_t n, double* V, double* part, const int* state, hipStream_t st) {
+    if (n <= 0) return hipErrorInvalidValue;
+    const int nb = miobi_norm_blocks(n);
+    k_miobi_colsq<<<nb, 256, 0, st>>>(n, V, part, state);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    k_miobi_scale<<<nb, 256, 0, st>>>(n, nb, V, part, state);
+    return hipGetLastError();
+}
+
+}  // namespace kt

@@ -394,3 +394,111 @@ def default_greedy_tol(A, rel=1e-6, ctx: Optional[Context] = None):
     """tol = 1e-6 * exp(normest(A)) as the greedy test drivers set it
     (Tests/test_unweighted_break.m:56,74: nrm = exp(normest(A, 1e-2)))."""
     return rel * float(np.exp(normest(A, 1e-2, ctx=ctx)))
+
+
+def pairs_score_topk(lam, V, P, sign=-2.0, ctx: Optional[Context] = None):
+    """The MIOBI score of every pair of P (npairs x 2, 0-based as entries_fun's
+    pairs) from t <= 32 eigenpairs: sum_k exp(lam[k]) exp(sign V[i, k] V[j, k])
+    (MIOBIBreakEdge2.m:60-68; sign = -2 scores removing the edge, +2 adding it,
+    MIOBIMakeEdge.m).  On the device (kt_pairs_score_topk); the t terms are
+    added in a fixed order."""
+    from .core import _colmajor, default_context
+    ctx = ctx or default_context()
+    lam = np.ascontiguousarray(np.asarray(lam, dtype=np.float64).ravel())
+    Vc = _colmajor(V)
+    if Vc.shape[1] != lam.size:
+        raise ValueError(f"pairs_score_topk: V has {Vc.shape[1]} columns, lam {lam.size} values")
+    P = np.asarray(P, dtype=np.int64).reshape(-1, 2)
+    _, pi = _i64(P[:, 0])
+    _, pj = _i64(P[:, 1])
+    score = np.zeros(max(P.shape[0], 1))
+    _lib.check(_lib.load().kt_pairs_score_topk(ctx.handle, Vc.shape[0], lam.size, _dptr(lam), _dptr(Vc), P.shape[0],
+                                               pi, pj, float(sign), _dptr(score)))
+    return score[:P.shape[0]]
+
+
+def _log_mean_exp(lam):
+    """log(mean(exp(lam))) as natural_connectivity_topk forms it."""
+    lam = np.asarray(lam, dtype=np.float64)
+    return float(np.log(np.sum(np.exp(lam - lam[0]))) + lam[0] - np.log(lam.size))
+
+
+def miobi_break(A, k, t=25, refresh=50, mode="reference", gap_rel=0.0, tol=0.0, max_spmm=0, seed=0,
+                return_V=False, ctx: Optional[Context] = None):
+    """MIOBI's top-t edge removal on the device (MIOBIBreakEdge2.m and
+    MIOBIBreakEdge2_weighted.m; kt_miobi_break): k times, score every edge with
+    the leading t eigenpairs, remove the lowest-scoring one and shift the
+    eigenvalues to first order; the eigenpairs are recomputed (eigs_topk with
+    tol, max_spmm, seed) after every refresh-th step, never with refresh <= 0
+    (the reference's 'NoUpdate' run; 50 is its 'Update50' run).  mode
+    "reference" keeps the vectors between recomputations, which is what the
+    reference's code computes; "paper" applies the first-order vector update it
+    meant to.  A DeviceMatrix is edited in place.
+
+    Returns (edges, info): edges as krylov_miobi returns them (1-based rows
+    (i, j), i >= j), fewer than k once no edge is left; info: "scores", "track"
+    (nsel + 1 rows of t eigenvalues: row s scores step s + 1), "nconv_min",
+    "refreshes", "R0" / "R1" = log(mean(exp(lam))) of eigs_topk(., t) before and
+    after, "rob_score" = (R0 - R1) 100 / R0 (:40-42, :266-268), "D" the edited
+    DeviceMatrix, and "V" (n x t, the vectors after the last step) with
+    return_V."""
+    from .core import eigs_topk
+    if mode not in ("reference", "paper"):
+        raise _lib.KrylovError(_lib.KT_ERR_ARG, "miobi_break: mode must be 'reference' or 'paper'")
+    D = _dev(A, ctx)
+    n, _ = D.info()
+    k, t = int(k), int(t)
+    cap = max(k, 1)
+    tt = max(t, 1)
+    si = np.zeros(cap, dtype=np.int64)
+    sj = np.zeros(cap, dtype=np.int64)
+    ss = np.zeros(cap)
+    track = np.zeros((cap + 1, tt))
+    Vf = np.zeros((max(n, 1), tt), order="F") if return_V else None
+    ns = C.c_int64()
+    ncm = C.c_int()
+    nrf = C.c_int()
+    p64 = C.POINTER(C.c_int64)
+    _lib.check(_lib.load().kt_miobi_break(
+        D.handle, k, t, int(refresh), 1 if mode == "paper" else 0, float(gap_rel), float(tol), int(max_spmm),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, si.ctypes.data_as(p64), sj.ctypes.data_as(p64), _dptr(ss), _dptr(track),
+        _dptr(Vf) if return_V else None, C.byref(ns), C.byref(ncm), C.byref(nrf)))
+    D.n, D.nnz = D.info()
+    m = int(ns.value)
+    if ncm.value < t:
+        warnings.warn(f"miobi_break: eigs_topk converged nconv = {ncm.value} of the {t} eigenpairs in at least one "
+                      "run; the scores use the pairs as returned", RuntimeWarning, stacklevel=2)
+    edges = np.stack([si[:m] + 1, sj[:m] + 1], axis=1)
+    lam1 = np.zeros(t) if D.nnz == 0 else eigs_topk(D, t, tol=tol, max_spmm=max_spmm, seed=seed, ctx=ctx)[0]
+    R0, R1 = _log_mean_exp(track[0]), _log_mean_exp(lam1)
+    info = {"scores": ss[:m].copy(), "track": track[:m + 1].copy(), "nconv_min": int(ncm.value),
+            "refreshes": int(nrf.value), "R0": R0, "R1": R1,
+            "rob_score": (R0 - R1) * 100.0 / R0 if R0 != 0.0 else 0.0, "D": D}
+    if return_V:
+        info["V"] = np.asarray(Vf[:n])
+    return edges, info
+
+
+def find_top_edges_miobi(A, num, t=25, tol=0.0, max_spmm=0, seed=0, ctx: Optional[Context] = None):
+    """The top `num` existing edges ranked by ascending MIOBI score (the edge
+    MIOBI would remove first comes first) from the leading t eigenpairs of
+    eigs_topk, column 0 by absolute value (MIOBIBreakEdge2.m:47-68), returned as
+    find_top_edges returns them: 1-based, i > j, enumerated in find(tril(A, -1))
+    order with ties kept in that order, and the same warning / error when fewer
+    than `num` edges exist -- a ranking greedy_krylov(..., top=...) takes."""
+    from .core import eigs_topk
+    D = _dev(A, ctx)
+    I, J = _tril_edges(D.to_scipy())
+    if len(I) < num:
+        warnings.warn("FIND_TOP_EDGES:: there are not enough edges in the graph")
+    num = int(np.floor(num))
+    if len(I) < num:
+        raise IndexError("FIND_TOP_EDGES:: there are not enough edges in the graph")
+    if len(I) == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    lam, V = eigs_topk(D, t, tol=tol, max_spmm=max_spmm, seed=seed, ctx=ctx)
+    V = np.array(V, order="F")
+    V[:, 0] = np.abs(V[:, 0])
+    score = pairs_score_topk(lam, V, np.stack([I, J], axis=1), sign=-2.0, ctx=D.ctx)
+    ind = _stable_head(score, num)
+    return np.stack([I[ind] + 1, J[ind] + 1], axis=1)

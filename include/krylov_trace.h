@@ -481,6 +481,37 @@ int kt_miobi_break(kt_matrix_t A, int k, int t, int refresh, int mode, double ga
                    int max_spmm, uint64_t seed, int64_t* sel_i, int64_t* sel_j, double* sel_score,
                    double* lambda_track, double* V_final, int64_t* nsel, int* nconv_min, int* refreshes);
 
+/* MIOBI's top-t edge addition (MIOBIMakeEdge.m, with t a parameter) with the
+ * step loop on the device: k times, take m = min(max degree + k, n) of the
+ * CURRENT matrix (k the whole budget), the first m nodes of a stable
+ * descending sort of |V(:, 1)| as candidates, score every non-adjacent pair of
+ * them, score = sum_{kappa < t} exp(lambda_kappa) exp(2 V[p, kappa] V[r, kappa]),
+ * add the pair with the largest score (exactly equal scores: the first in the
+ * reference's enumeration, rank of p ascending, then rank of r), and shift the
+ * eigenvalues to first order, lambda_kappa += 2 V[p, kappa] V[r, kappa].  The
+ * vectors stay as computed between two recomputations, which is what the
+ * reference's update amounts to; there is no `paper`
+ * mode.  refresh > 0: after every refresh-th step but the last the eigenpairs
+ * are recomputed on the edited matrix (kt_eigs_topk with tol, max_spmm, seed);
+ * refresh <= 0: never.  The steps between two recomputations are queued
+ * without a host synchronisation.  A must hold unit weights (the reference
+ * binarises its input) and at least one entry; it is edited in place (the
+ * selected pairs set to 1).
+ * Outputs: sel_i >= sel_j (0-based) and sel_score, k each; lambda_track
+ * (nullable), (k + 1) x t ROW-major: row s = the eigenvalues that score step
+ * s + 1 (a recomputation replaces its step's row); cand_m (nullable, k ints):
+ * the m of every step; *nsel < k once no non-adjacent candidate pair is left;
+ * *nconv_min (nullable) the smallest nconv a kt_eigs_topk run returned;
+ * *refreshes (nullable) the recomputations.  The same arguments give the same
+ * bits.  KT_ERR_ARG before the device is touched for NULL arguments, k < 0, t
+ * outside 2..min(32, n), a matrix that is empty or not unit-weight, or
+ * outstanding kt_slq_submit calls; KT_ERR_NOT_HERMITIAN for non-symmetric A;
+ * KT_ERR_ALLOC if the candidate block (m x m / 8 bytes of adjacency bits) does
+ * not fit.  On any error A is left as it was. */
+int kt_miobi_make(kt_matrix_t A, int k, int t, int refresh, double tol, int max_spmm, uint64_t seed,
+                  int64_t* sel_i, int64_t* sel_j, double* sel_score, double* lambda_track,
+                  int* cand_m, int64_t* nsel, int* nconv_min, int* refreshes);
+
 /* Per-kernel timing (HIP events recorded on the library's stream around each
  * launch of the named kernel while enabled).  kernel: 0 = the probe-Lanczos
  * gather pass (k_spmm_lanczos in the y-form sweep, k_spmm_dot = K1 in the
@@ -502,7 +533,9 @@ int kt_miobi_break(kt_matrix_t A, int k, int t, int refresh, int mode, double ga
  * block-Krylov paths' own and are not event-timed),
  * 11 = kt_miobi_break's steps, one interval per step (k_miobi_score,
  * k_miobi_pick and, in mode 1, the rotation and normalisation), and
- * kt_pairs_score_topk's scoring launch.
+ * kt_pairs_score_topk's scoring launch,
+ * 12 = kt_miobi_make's steps, one interval per step (k_miobi_make_score,
+ * k_miobi_make_pick).
  * Returns launch count and summed milliseconds. */
 int kt_profile_enable(kt_context_t ctx, int enable);
 int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* total_ms);
@@ -539,7 +572,10 @@ int kt_debug_delay(kt_context_t ctx, int lane, double microseconds);
  * off), since context creation.  stat 8: y-form step passes queued by
  * kt_slq_trace_auto calls (those queued past a sweep's last stop, which
  * return at once, included), since context creation.  stat 9: thick restarts
- * of kt_eigs_topk calls, since context creation. */
+ * of kt_eigs_topk calls, since context creation.  stats 10, 11, 12: host
+ * microseconds of the last kt_miobi_make call on this context -- its
+ * eigensolver runs; its candidate ranking, mask construction and uploads; its
+ * edits of A. */
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value);
 
 /* Threads of the process-wide host pool (the per-column / per-candidate

@@ -266,6 +266,29 @@ hipError_t launch_miobi_pick(int nparts, const double* part_s, const unsigned lo
                              hipStream_t st);
 int miobi_norm_blocks(int64_t n);
 hipError_t launch_miobi_normalise(int64_t n, double* V, double* part, const int* state, hipStream_t st);
+// MIOBI make-edge (kt_miobi_make).  W: the candidates' rows of
+// V, mcap x kMiobiLd row-major in RANK order, columns >= t zero; mask: mcap rows
+// of miobi_make_words(mcap) 64-bit words, bit (a, b) = "ranks a and b are
+// adjacent" (both halves); state = {steps, stop, maxdeg, live m}.
+// launch_miobi_make_score scores every pair of ranks a < b < state[3] whose
+// mask bit is clear, score = sum_{k < t} c[k] exp(2 W[a, k] W[b, k]), over 64 x
+// 64 tiles of the rank square; nblocks = miobi_make_blocks(mcap, max_blocks)
+// workgroups each leave their first candidate (largest score, exactly equal
+// scores by the smaller key (a << 32) | b; part_ok 0: none) in part_*[b].
+// score (nullable) is mcap x mcap row-major and receives the scored pairs.
+// launch_miobi_make_pick reduces the candidates and applies the step (see the
+// kernel).  A set state[1] makes both a no-op.
+constexpr int kMiobiMakeTile = 64;   // ranks along each side of a workgroup's tile
+inline int miobi_make_words(int mcap) { return (mcap + 63) / 64; }
+int miobi_make_blocks(int mcap, int max_blocks);
+hipError_t launch_miobi_make_score(int mcap, int t, const double* W, const double* c,
+                                   const unsigned long long* mask, const int* state, double* score, int nblocks,
+                                   double* part_s, unsigned long long* part_key, int* part_ok, hipStream_t st);
+hipError_t launch_miobi_make_pick(int nparts, const double* part_s, const unsigned long long* part_key,
+                                  const int* part_ok, int mcap, int t, int k, int n, const double* W,
+                                  const int* node, double* e, double* c, unsigned long long* mask, int* deg,
+                                  int* sel_i, int* sel_j, double* sel_score, double* track, int* cand_m,
+                                  int* state, hipStream_t st);
 int inf_norm_blocks();
 // normest1 (t = 1) reductions, normest1_blocks(n) partials each: sum |Y| in
 // partial[0, nb), S_prev . S in partial[nb, 2 nb), S = mysign(Y); per-block

@@ -1,6 +1,7 @@
 // kt_miobi.cpp -- kt_miobi_break and kt_pairs_score_topk: MIOBI's top-t edge
 // removal (MIOBIBreakEdge2.m / MIOBIBreakEdge2_weighted.m) with the step loop
-// on the device (kernels in kt_miobi.hip).
+// on the device (kernels in kt_miobi.hip); and kt_miobi_make,
+// its edge addition (MIOBIMakeEdge.m), at the end of the file.
 //
 // A window is the run of steps between two eigenpair recomputations.  Its
 // steps are queued back to back -- per step k_miobi_score over the pair list
@@ -10,6 +11,7 @@
 // read back once, at the window's end.  A recomputation applies the window's
 // removals to A through set_pairs and runs eigs_topk_impl on the edited matrix.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -17,6 +19,7 @@
 #include "kt_block.h"
 #include "kt_krylov.h"
 #include "kt_launch.h"
+#include "kt_miobi_host.h"
 
 namespace kt {
 
@@ -237,6 +240,164 @@ void pairs_score_impl(kt_context_s* ctx, int64_t n, int t, const double* lambda,
     KT_HIP(hipStreamSynchronize(st));
 }
 
+// kt_miobi_make past its argument checks (MIOBIMakeEdge.m with t a parameter).
+// Per window (the steps between two eigenpair recomputations): the eigenpairs,
+// the candidate ranking by |V(:, 1)| and, for the mcap ranks the window can
+// reach, the rows of V, node ids, degrees and adjacency bitmask go up; the
+// window's steps (k_miobi_make_score, k_miobi_make_pick) are queued back to
+// back; selections, scores, track rows, the m of every step and the state come
+// back once, and the additions go into A through set_pairs.  The vectors stay
+// as computed between recomputations (what the reference's update amounts to,
+// §4.2e), so the ranking is the window's.  added_i / added_j: every pair handed
+// to set_pairs so far (the caller removes them again on an error).
+void miobi_make_impl(kt_matrix_s* A, int k, int t, int refresh, double tol, int max_spmm, uint64_t seed,
+                     int64_t* sel_i, int64_t* sel_j, double* sel_score, double* track, int* cand_m, int64_t* nsel,
+                     int* nconv_min, int* refreshes, std::vector<int64_t>& added_i, std::vector<int64_t>& added_j) {
+    kt_context_s* ctx = A->ctx;
+    const int64_t n = A->n;
+    *nsel = 0;
+    if (nconv_min) *nconv_min = t;
+    if (refreshes) *refreshes = 0;
+    if (track) std::fill(track, track + (size_t)(k + 1) * t, 0.0);
+    if (cand_m) std::fill(cand_m, cand_m + k, 0);
+
+    KT_HIP(hipSetDevice(ctx->device));
+    prof_recycle(ctx);
+    // host time by part (kt_context_stat 10-12)
+    ctx->make_eig_us = ctx->make_rank_us = ctx->make_edit_us = 0;
+    auto mark = std::chrono::steady_clock::now();
+    const auto lap = [&mark](int64_t& into) {
+        const auto now = std::chrono::steady_clock::now();
+        into += std::chrono::duration_cast<std::chrono::microseconds>(now - mark).count();
+        mark = now;
+    };
+    std::vector<double> lam(t), Vh((size_t)n * t), v0((size_t)n);
+    int nconv = 0, nc_min;
+    eigs_topk_impl(A, t, tol, max_spmm, seed, lam.data(), Vh.data(), nullptr, &nconv, nullptr);
+    lap(ctx->make_eig_us);
+    nc_min = nconv;
+    if (track) std::copy(lam.begin(), lam.end(), track);
+
+    // the maximum degree grows by at most one per step, so no window's mcap
+    // exceeds min(maxdeg + 2 k, n): one allocation serves them all
+    int maxdeg = miobi_max_degree(n, A->h_rowptr.data());
+    const int kk = std::max(k, 1);
+    const int64_t mcap_max = std::max(2, miobi_cap_m(maxdeg, k, k, n)), words_max = (mcap_max + 63) / 64;
+    Carver cv;
+    const size_t oE = cv.take(sizeof(double) * kLd), oC = cv.take(sizeof(double) * kLd),
+                 oPs = cv.take(sizeof(double) * kMiobiMaxBlocks),
+                 oPk = cv.take(sizeof(unsigned long long) * kMiobiMaxBlocks),
+                 oPo = cv.take(sizeof(int) * kMiobiMaxBlocks), oSt = cv.take(sizeof(int) * 4),
+                 oSi = cv.take(sizeof(int) * kk), oSj = cv.take(sizeof(int) * kk),
+                 oSs = cv.take(sizeof(double) * kk), oCm = cv.take(sizeof(int) * kk),
+                 oTr = cv.take(sizeof(double) * kLd * (kk + 1)), oW = cv.take(sizeof(double) * kLd * mcap_max),
+                 oNd = cv.take(sizeof(int) * mcap_max), oDg = cv.take(sizeof(int) * mcap_max),
+                 oMk = cv.take(sizeof(unsigned long long) * mcap_max * words_max);
+    if (cv.bytes / 8 > (size_t)INT32_MAX)
+        fail(KT_ERR_ALLOC, "kt_miobi_make: the candidate block's adjacency mask does not fit the pool");
+    Block blk;
+    blk.alloc(ctx, cv.bytes);
+    double *dE = blk.at<double>(oE), *dC = blk.at<double>(oC), *dPs = blk.at<double>(oPs);
+    double *dSs = blk.at<double>(oSs), *dTr = blk.at<double>(oTr), *dW = blk.at<double>(oW);
+    unsigned long long *dPk = blk.at<unsigned long long>(oPk), *dMk = blk.at<unsigned long long>(oMk);
+    int *dPo = blk.at<int>(oPo), *dSt = blk.at<int>(oSt), *dSi = blk.at<int>(oSi), *dSj = blk.at<int>(oSj);
+    int *dCm = blk.at<int>(oCm), *dNd = blk.at<int>(oNd), *dDg = blk.at<int>(oDg);
+    hipStream_t st = ctx->stream;
+    KT_HIP(hipMemsetAsync(dTr, 0, sizeof(double) * kLd * (kk + 1), st));
+
+    std::vector<int> hsi(kk), hsj(kk), hcm(kk), node, rank_of((size_t)n, -1), hdeg;
+    std::vector<double> hss(kk), htr((size_t)kLd * (kk + 1)), hW;
+    std::vector<uint64_t> hmask;
+    std::vector<int64_t> ei, ej;
+    int done = 0, nref = 0;
+    while (done < k) {
+        int w = k - done;
+        if (refresh > 0) w = std::min(w, refresh - done % refresh);
+        mark = std::chrono::steady_clock::now();
+        // :49, :60-64  column 0 by absolute value, the ranking, the ranks in reach
+        const int mcap = miobi_cap_m(maxdeg, k, w, n), words = miobi_make_words(mcap);
+        for (int64_t i = 0; i < n; ++i) v0[(size_t)i] = std::fabs(Vh[(size_t)i]);
+        miobi_rank(n, v0.data(), mcap, node);
+        miobi_set_ranks(node, rank_of, true);
+        miobi_build_mask(A->h_rowptr.data(), A->h_col.data(), node, rank_of, hmask, hdeg);
+        hW.assign((size_t)mcap * kLd, 0.0);
+        for (int a = 0; a < mcap; ++a)
+            for (int c = 0; c < t; ++c) {
+                const double x = Vh[(size_t)node[a] + (size_t)c * n];
+                hW[(size_t)a * kLd + c] = c == 0 ? std::fabs(x) : x;
+            }
+        int hm = miobi_live_m(maxdeg, k, n), hmax = maxdeg;
+        int state[4] = {done, 0, maxdeg, hm};
+        KT_HIP(hipMemcpyAsync(dW, hW.data(), sizeof(double) * hW.size(), hipMemcpyHostToDevice, st));
+        KT_HIP(hipMemcpyAsync(dNd, node.data(), sizeof(int) * mcap, hipMemcpyHostToDevice, st));
+        KT_HIP(hipMemcpyAsync(dDg, hdeg.data(), sizeof(int) * mcap, hipMemcpyHostToDevice, st));
+        KT_HIP(hipMemcpyAsync(dMk, hmask.data(), sizeof(uint64_t) * (size_t)mcap * words, hipMemcpyHostToDevice, st));
+        KT_HIP(hipMemcpyAsync(dSt, state, sizeof state, hipMemcpyHostToDevice, st));
+        upload_e(ctx, t, lam.data(), dE, dC);  // (synchronises: the host buffers above are free again)
+        lap(ctx->make_rank_us);
+
+        const int nblocks = miobi_make_blocks(mcap, 0);
+        for (int s = 0; s < w; ++s) {
+            prof_begin(ctx, PROF_MIOBI_MAKE, st, t);
+            KT_HIP(launch_miobi_make_score(mcap, t, dW, dC, dMk, dSt, nullptr, nblocks, dPs, dPk, dPo, st));
+            KT_HIP(launch_miobi_make_pick(nblocks, dPs, dPk, dPo, mcap, t, k, (int)n, dW, dNd, dE, dC, dMk, dDg, dSi,
+                                          dSj, dSs, dTr, dCm, dSt, st));
+            prof_end(ctx, PROF_MIOBI_MAKE, st);
+        }
+        KT_HIP(hipMemcpyAsync(state, dSt, sizeof state, hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(hsi.data() + done, dSi + done, sizeof(int) * w, hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(hsj.data() + done, dSj + done, sizeof(int) * w, hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(hss.data() + done, dSs + done, sizeof(double) * w, hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(hcm.data() + done, dCm + done, sizeof(int) * w, hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(htr.data() + (size_t)kLd * (done + 1), dTr + (size_t)kLd * (done + 1),
+                              sizeof(double) * kLd * w, hipMemcpyDeviceToHost, st));
+        KT_HIP(hipStreamSynchronize(st));
+        const int now = state[0];
+        if (now < done || now > done + w) fail(KT_ERR_HIP, "kt_miobi_make: the device step count is out of range");
+        ei.clear();
+        ej.clear();
+        for (int s = done; s < now; ++s) {
+            // the device's m bookkeeping replayed on the host
+            const bool inside = hsi[s] >= 0 && hsi[s] < n && hsj[s] >= 0 && hsj[s] < hsi[s];
+            const int a = inside ? rank_of[(size_t)hsi[s]] : -1, b = inside ? rank_of[(size_t)hsj[s]] : -1;
+            if (a < 0 || b < 0) fail(KT_ERR_HIP, "kt_miobi_make: the device selected a pair outside the candidates");
+            if (hcm[s] != hm) fail(KT_ERR_HIP, "kt_miobi_make: the device's candidate count differs from the host's");
+            hm = miobi_book_step(hdeg, hmax, a, b, k, n);
+            sel_i[s] = hsi[s];
+            sel_j[s] = hsj[s];
+            sel_score[s] = hss[s];
+            if (cand_m) cand_m[s] = hcm[s];
+            if (track) std::copy(htr.begin() + (size_t)kLd * (s + 1), htr.begin() + (size_t)kLd * (s + 1) + t,
+                                 track + (size_t)(s + 1) * t);
+            ei.push_back(hsi[s]);
+            ej.push_back(hsj[s]);
+        }
+        miobi_set_ranks(node, rank_of, false);
+        if (!ei.empty()) {
+            added_i.insert(added_i.end(), ei.begin(), ei.end());
+            added_j.insert(added_j.end(), ej.begin(), ej.end());
+            mark = std::chrono::steady_clock::now();
+            set_pairs(A, (int64_t)ei.size(), ei.data(), ej.data(), 1.0);
+            lap(ctx->make_edit_us);
+        }
+        maxdeg = miobi_max_degree(n, A->h_rowptr.data());
+        if (state[2] != hmax || maxdeg != hmax)
+            fail(KT_ERR_HIP, "kt_miobi_make: the device's maximum degree differs from the host rows'");
+        done = now;
+        *nsel = done;
+        if (state[1] || done >= k) break;
+        // :326-331  the eigenpairs of the edited matrix
+        mark = std::chrono::steady_clock::now();
+        eigs_topk_impl(A, t, tol, max_spmm, seed, lam.data(), Vh.data(), nullptr, &nconv, nullptr);
+        lap(ctx->make_eig_us);
+        nc_min = std::min(nc_min, nconv);
+        ++nref;
+        if (track) std::copy(lam.begin(), lam.end(), track + (size_t)done * t);
+    }
+    if (nconv_min) *nconv_min = nc_min;
+    if (refreshes) *refreshes = nref;
+}
+
 }  // namespace
 
 }  // namespace kt
@@ -287,6 +448,39 @@ extern "C" int kt_miobi_break(kt_matrix_t A, int k, int t, int refresh, int mode
             fail(KT_ERR_ARG, "kt_miobi_break: kt_slq_submit calls are outstanding on this context");
         miobi_break_impl(A, k, t, refresh, mode, gap_rel, tol, max_spmm, seed, sel_i, sel_j, sel_score, lambda_track,
                          V_final, nsel, nconv_min, refreshes);
+    }
+    KT_MIOBI_GUARD_END
+}
+
+extern "C" int kt_miobi_make(kt_matrix_t A, int k, int t, int refresh, double tol, int max_spmm, uint64_t seed,
+                             int64_t* sel_i, int64_t* sel_j, double* sel_score, double* lambda_track, int* cand_m,
+                             int64_t* nsel, int* nconv_min, int* refreshes) {
+    std::vector<int64_t> added_i, added_j;
+    try {
+        try {
+            if (!A || !nsel || (k > 0 && (!sel_i || !sel_j || !sel_score)))
+                fail(KT_ERR_ARG, "kt_miobi_make: NULL argument");
+            if (k < 0) fail(KT_ERR_ARG, "kt_miobi_make: k must not be negative");
+            if (t < 2 || t > kMiobiLd || t > A->n) fail(KT_ERR_ARG, "kt_miobi_make: t must be in [2, min(32, n)]");
+            if (A->nnz == 0 || !A->unit_values)
+                fail(KT_ERR_ARG, "kt_miobi_make: the matrix must be a unit-weight adjacency matrix with at least one "
+                                 "edge (MIOBIMakeEdge.m binarises its input)");
+            if (A->ctx->ws.slq_submitted != A->ctx->ws.slq_collected)
+                fail(KT_ERR_ARG, "kt_miobi_make: kt_slq_submit calls are outstanding on this context");
+            require_symmetric(A, "MIOBI:: adjacency matrix has to be symmetric");
+            miobi_make_impl(A, k, t, refresh, tol, max_spmm, seed, sel_i, sel_j, sel_score, lambda_track, cand_m, nsel,
+                            nconv_min, refreshes, added_i, added_j);
+        } catch (...) {
+            // on any error the matrix stays as it was: the pairs added so far were non-adjacent
+            if (!added_i.empty()) {
+                try {
+                    set_pairs(A, (int64_t)added_i.size(), added_i.data(), added_j.data(), 0.0);
+                } catch (...) {
+                }
+                *nsel = 0;
+            }
+            throw;
+        }
     }
     KT_MIOBI_GUARD_END
 }

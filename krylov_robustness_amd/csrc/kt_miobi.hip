@@ -1,7 +1,9 @@
 // kt_miobi.hip -- the kernels of kt_miobi_break and kt_pairs_score_topk
 // (kt_miobi.cpp): the MIOBI edge score from the top-t
 // eigenpairs on a pair list, the global argmin with the step applied on the
-// device, and the column normalisation of the `paper` eigenvector update.
+// device, and the column normalisation of the `paper` eigenvector update; and,
+// at the end of the file, the two kernels of kt_miobi_make (§4.2f): the scores
+// of a dense block of candidate pairs from LDS tiles, and its argmax and step.
 //
 // V is n x 32 row-major in ORIGINAL numbering (t <= 32 live columns, the rest
 // zero): one row is 256 bytes, so a half-wave with lane = column reads a row
@@ -321,6 +323,252 @@ hipError_t launch_miobi_normalise(int64_t n, double* V, double* part, const int*
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     k_miobi_scale<<<nb, 256, 0, st>>>(n, nb, V, part, state);
+    return hipGetLastError();
+}
+
+// ---- make-edge (kt_miobi_make, MIOBIMakeEdge.m) -----------
+
+namespace {
+
+constexpr int kMT = kMiobiMakeTile;
+// a panel is stored [k][rank] with the rank stride padded by one double: the
+// transposing store (lane = k, stride kPanelLd doubles) then spreads over the
+// banks, and the reads (consecutive ranks, or one address per wave row) stay
+// conflict-free
+constexpr int kPanelLd = kMT + 1;
+
+// (s1, k1) before (s2, k2): the LARGER score, exactly equal scores by the
+// smaller key (rank_a << 32) | rank_b -- the reference's first maximum in its
+// a-then-b enumeration (MIOBIMakeEdge.m:72-80, :97).  ok = 0: no candidate.
+// A NaN score loses to every number.
+__device__ __forceinline__ bool make_before(double s1, u64 k1, int ok1, double s2, u64 k2, int ok2) {
+    if (!ok1) return false;
+    if (!ok2) return true;
+    const bool n1 = s1 != s1, n2 = s2 != s2;
+    if (n1 != n2) return n2;
+    if (!n1 && s1 != s2) return s1 > s2;
+    return k1 < k2;
+}
+
+}  // namespace
+
+// The hot path: every non-adjacent pair of ranks a < b < m (m = state[3], the
+// live candidate count) scored from the candidates' rows W,
+//   score(a, b) = sum_{k < t} c[k] exp(2 W[a, k] W[b, k]),   k ascending.
+// A workgroup takes 64 x 64 tiles (tile row <= tile column) of the rank square,
+// grid-striding over the linear index L = tc (tc + 1) / 2 + tr.  The tile's two
+// 64 x 32 panels are staged in LDS as [k][rank]; thread (tx, ty) owns the 4 x 4
+// pairs (a0 + ty + 16 u, b0 + tx + 16 v): per k it reads 4 + 4 doubles (the b
+// reads are 16 consecutive doubles per wave row, the a reads one address per
+// wave row) and does 16 exp + 16 fma, one accumulator per pair.  No atomics and
+// no cross-lane sums: a pair's bits depend on W, c and t only.  A pair is
+// skipped on or below the diagonal, at or beyond m, or with its mask bit set
+// (word tc of row a: one word per row per tile); a thread with no pair left
+// skips the k loop, a tile at or beyond m is skipped by the whole workgroup.
+// part_*[blockIdx.x]: the workgroup's first candidate under make_before().
+__global__ __launch_bounds__(256) void k_miobi_make_score(int mcap, int t, const double* __restrict__ W,
+                                                          const double* __restrict__ c,
+                                                          const u64* __restrict__ mask,
+                                                          const int* __restrict__ state, double* __restrict__ score,
+                                                          double* __restrict__ part_s, u64* __restrict__ part_key,
+                                                          int* __restrict__ part_ok) {
+    if (state[1]) return;  // the same word for every thread
+    __shared__ double sA[kLd * kPanelLd], sB[kLd * kPanelLd];
+    __shared__ u64 sM[kMT];
+    __shared__ double sc[kLd];
+    __shared__ double red_s[256];
+    __shared__ u64 red_k[256];
+    __shared__ int red_o[256];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int m = min(state[3], mcap);
+    const int words = (mcap + kMT - 1) / kMT;  // tiles per side = mask words per row
+    const int64_t ntiles = (int64_t)words * (words + 1) / 2;
+    if (tid < kLd) sc[tid] = tid < t ? c[tid] : 0.0;
+    double bs = 0.0;
+    u64 bk = 0;
+    int bo = 0;
+    for (int64_t L = blockIdx.x; L < ntiles; L += gridDim.x) {  // workgroup-uniform trip count
+        int tc = (int)((sqrt(8.0 * (double)L + 1.0) - 1.0) * 0.5);
+        while ((int64_t)tc * (tc + 1) / 2 > L) --tc;
+        while ((int64_t)(tc + 1) * (tc + 2) / 2 <= L) ++tc;
+        const int tr = (int)(L - (int64_t)tc * (tc + 1) / 2);
+        const int a0 = tr * kMT, b0 = tc * kMT;
+        if (b0 >= m) continue;  // no pair with b < m: the whole workgroup skips
+        __syncthreads();        // the previous tile's panels have been read
+        for (int q = tid; q < kMT * kLd; q += 256) {
+            const int row = q >> 5, kk = q & 31;
+            sA[kk * kPanelLd + row] = a0 + row < mcap ? W[(int64_t)(a0 + row) * kLd + kk] : 0.0;
+            sB[kk * kPanelLd + row] = b0 + row < mcap ? W[(int64_t)(b0 + row) * kLd + kk] : 0.0;
+        }
+        if (tid < kMT) sM[tid] = a0 + tid < mcap ? mask[(int64_t)(a0 + tid) * words + tc] : ~0ull;
+        __syncthreads();
+        unsigned live = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int ra = a0 + ty + 16 * u;
+            const u64 mw = sM[ty + 16 * u];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int rb = b0 + tx + 16 * v;
+                if (ra < rb && rb < m && !((mw >> (tx + 16 * v)) & 1ull)) live |= 1u << (u * 4 + v);
+            }
+        }
+        if (live) {
+            double acc[4][4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) acc[u][v] = 0.0;
+            for (int kk = 0; kk < t; ++kk) {
+                const double ck = sc[kk];
+                double a[4], b[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) a[u] = sA[kk * kPanelLd + ty + 16 * u];
+#pragma unroll
+                for (int v = 0; v < 4; ++v) b[v] = sB[kk * kPanelLd + tx + 16 * v];
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) acc[u][v] = fma(ck, exp(2.0 * (a[u] * b[v])), acc[u][v]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int v = 0; v < 4; ++v)
+                    if (live & (1u << (u * 4 + v))) {
+                        const int ra = a0 + ty + 16 * u, rb = b0 + tx + 16 * v;
+                        const double s = acc[u][v];
+                        const u64 key = ((u64)(unsigned)ra << 32) | (unsigned)rb;
+                        if (score) score[(int64_t)ra * mcap + rb] = s;
+                        if (make_before(s, key, 1, bs, bk, bo)) {
+                            bs = s;
+                            bk = key;
+                            bo = 1;
+                        }
+                    }
+        }
+    }
+    red_s[tid] = bs;
+    red_k[tid] = bk;
+    red_o[tid] = bo;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w && make_before(red_s[tid + w], red_k[tid + w], red_o[tid + w], red_s[tid], red_k[tid], red_o[tid])) {
+            red_s[tid] = red_s[tid + w];
+            red_k[tid] = red_k[tid + w];
+            red_o[tid] = red_o[tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        part_s[blockIdx.x] = red_s[0];
+        part_key[blockIdx.x] = red_k[0];
+        part_ok[blockIdx.x] = red_o[0];
+    }
+}
+
+int miobi_make_blocks(int mcap, int max_blocks) {
+    const int64_t side = (mcap + kMT - 1) / kMT, ntiles = side * (side + 1) / 2;
+    const int cap = max_blocks > 0 ? std::min(max_blocks, kMiobiMaxBlocks) : kMiobiMaxBlocks;
+    return (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, cap));
+}
+
+hipError_t launch_miobi_make_score(int mcap, int t, const double* W, const double* c,
+                                   const unsigned long long* mask, const int* state, double* score, int nblocks,
+                                   double* part_s, unsigned long long* part_key, int* part_ok, hipStream_t st) {
+    if (mcap < 2 || t < 1 || t > kLd || nblocks < 1 || nblocks > kMiobiMaxBlocks) return hipErrorInvalidValue;
+    k_miobi_make_score<<<nblocks, 256, 0, st>>>(mcap, t, W, c, mask, state, score, part_s, part_key, part_ok);
+    return hipGetLastError();
+}
+
+// One workgroup: the first of the nparts workgroup candidates under
+// make_before(), then the step (MIOBIMakeEdge.m:97-118): with (a, b) the ranks,
+// (i, j) = (node[a], node[b]) and s = state[0] the steps so far,
+//   sel_i[s] = max(i, j), sel_j[s] = min(i, j), sel_score[s] = the score,
+//   cand_m[s] = state[3], the m this step scored with,
+//   mask bits (a, b) and (b, a) set,
+//   e[k] += 2 W[a, k] W[b, k], c[k] = exp(e[k]), track[(s + 1) 32 + k] = e[k]  (k < t),
+//   deg[a]++, deg[b]++, state[2] = maxdeg = max(maxdeg, deg[a], deg[b]),
+//   state[3] = min(maxdeg + k, n) (<= mcap by the driver's construction, and
+//   held to it), state[0] = s + 1.
+// No candidate: state[1] = 1 and nothing else; a launch that finds state[1] set
+// returns at once.
+__global__ __launch_bounds__(256) void k_miobi_make_pick(int nparts, const double* __restrict__ part_s,
+                                                         const u64* __restrict__ part_key,
+                                                         const int* __restrict__ part_ok, int mcap, int t, int k,
+                                                         int n, const double* __restrict__ W,
+                                                         const int* __restrict__ node, double* __restrict__ e,
+                                                         double* __restrict__ c, u64* __restrict__ mask,
+                                                         int* __restrict__ deg, int* __restrict__ sel_i,
+                                                         int* __restrict__ sel_j, double* __restrict__ sel_score,
+                                                         double* __restrict__ track, int* __restrict__ cand_m,
+                                                         int* __restrict__ state) {
+    if (state[1]) return;
+    __shared__ double ss[256];
+    __shared__ u64 sk[256];
+    __shared__ int so[256];
+    const int tid = threadIdx.x;
+    const int step = state[0], maxdeg = state[2], m_used = state[3];
+    double bs = 0.0;
+    u64 bk = 0;
+    int bo = 0;
+    for (int q = tid; q < nparts; q += 256)
+        if (make_before(part_s[q], part_key[q], part_ok[q], bs, bk, bo)) {
+            bs = part_s[q];
+            bk = part_key[q];
+            bo = 1;
+        }
+    ss[tid] = bs;
+    sk[tid] = bk;
+    so[tid] = bo;
+    __syncthreads();  // every thread has read the state words
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w && make_before(ss[tid + w], sk[tid + w], so[tid + w], ss[tid], sk[tid], so[tid])) {
+            ss[tid] = ss[tid + w];
+            sk[tid] = sk[tid + w];
+            so[tid] = so[tid + w];
+        }
+        __syncthreads();
+    }
+    const int a = (int)(sk[0] >> 32), b = (int)(sk[0] & 0xffffffffull);
+    if (!so[0] || a < 0 || a >= b || b >= mcap) {  // (a key outside the rank square cannot come from the score kernel)
+        if (tid == 0) state[1] = 1;
+        return;
+    }
+    if (tid < t) {
+        const double en = e[tid] + 2.0 * (W[(int64_t)a * kLd + tid] * W[(int64_t)b * kLd + tid]);
+        e[tid] = en;
+        c[tid] = exp(en);
+        track[(int64_t)(step + 1) * kLd + tid] = en;
+    }
+    if (tid == 0) {
+        const int words = (mcap + kMT - 1) / kMT;
+        const int i = node[a], j = node[b];
+        sel_i[step] = max(i, j);
+        sel_j[step] = min(i, j);
+        sel_score[step] = ss[0];
+        cand_m[step] = m_used;
+        mask[(int64_t)a * words + (b >> 6)] |= 1ull << (b & 63);
+        mask[(int64_t)b * words + (a >> 6)] |= 1ull << (a & 63);
+        const int da = deg[a] + 1, db = deg[b] + 1;
+        deg[a] = da;
+        deg[b] = db;
+        const int md = max(maxdeg, max(da, db));
+        state[2] = md;
+        state[3] = (int)min((int64_t)mcap, min((int64_t)md + k, (int64_t)n));
+        state[0] = step + 1;
+    }
+}
+
+hipError_t launch_miobi_make_pick(int nparts, const double* part_s, const unsigned long long* part_key,
+                                  const int* part_ok, int mcap, int t, int k, int n, const double* W,
+                                  const int* node, double* e, double* c, unsigned long long* mask, int* deg,
+                                  int* sel_i, int* sel_j, double* sel_score, double* track, int* cand_m,
+                                  int* state, hipStream_t st) {
+    if (nparts < 1 || nparts > kMiobiMaxBlocks || mcap < 2 || t < 1 || t > kLd || k < 0 || n < mcap)
+        return hipErrorInvalidValue;
+    k_miobi_make_pick<<<1, 256, 0, st>>>(nparts, part_s, part_key, part_ok, mcap, t, k, n, W, node, e, c, mask, deg,
+                                         sel_i, sel_j, sel_score, track, cand_m, state);
     return hipGetLastError();
 }
 

@@ -479,6 +479,58 @@ def miobi_break(A, k, t=25, refresh=50, mode="reference", gap_rel=0.0, tol=0.0, 
     return edges, info
 
 
+def miobi_make(A, k, t=25, refresh=50, tol=0.0, max_spmm=0, seed=0, ctx: Optional[Context] = None):
+    """MIOBI's top-t edge addition on the device (MIOBIMakeEdge.m with t a
+    parameter; kt_miobi_make): k times, take the m = min(max degree + k, n)
+    nodes with the largest |V(:, 1)| as candidates (k the whole budget, the
+    degree of the current matrix), score every non-adjacent pair of them with
+    the leading t eigenpairs, add the highest-scoring one and shift the
+    eigenvalues to first order; the eigenpairs are recomputed (eigs_topk with
+    tol, max_spmm, seed) after every refresh-th step, never with refresh <= 0
+    (the reference's 'NoUpdate' run; 50 is its 'Update50' run).  The vectors
+    stay as computed between recomputations, which is what the reference's
+    code computes.  A must hold unit weights; a DeviceMatrix
+    is edited in place.
+
+    Returns (edges, info): edges as krylov_miobi returns them (1-based rows
+    (i, j), i > j), fewer than k once no non-adjacent candidate pair is left;
+    info: "scores", "track" (nsel + 1 rows of t eigenvalues: row s scores step
+    s + 1), "m" (the candidate count of every step), "nconv_min", "refreshes",
+    "R0" / "R1" = log(mean(exp(lam))) of eigs_topk(., t) before and after,
+    "rob_score" = (R1 - R0) 100 / R0 (:44, :186-188), and "D" the edited
+    DeviceMatrix."""
+    from .core import eigs_topk
+    D = _dev(A, ctx)
+    k, t = int(k), int(t)
+    cap = max(k, 1)
+    tt = max(t, 1)
+    si = np.zeros(cap, dtype=np.int64)
+    sj = np.zeros(cap, dtype=np.int64)
+    ss = np.zeros(cap)
+    cm = np.zeros(cap, dtype=np.int32)
+    track = np.zeros((cap + 1, tt))
+    ns = C.c_int64()
+    ncm = C.c_int()
+    nrf = C.c_int()
+    p64 = C.POINTER(C.c_int64)
+    _lib.check(_lib.load().kt_miobi_make(
+        D.handle, k, t, int(refresh), float(tol), int(max_spmm), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        si.ctypes.data_as(p64), sj.ctypes.data_as(p64), _dptr(ss), _dptr(track),
+        cm.ctypes.data_as(C.POINTER(C.c_int)), C.byref(ns), C.byref(ncm), C.byref(nrf)))
+    D.n, D.nnz = D.info()
+    m = int(ns.value)
+    if ncm.value < t:
+        warnings.warn(f"miobi_make: eigs_topk converged nconv = {ncm.value} of the {t} eigenpairs in at least one "
+                      "run; the scores use the pairs as returned", RuntimeWarning, stacklevel=2)
+    edges = np.stack([si[:m] + 1, sj[:m] + 1], axis=1)
+    lam1 = eigs_topk(D, t, tol=tol, max_spmm=max_spmm, seed=seed, ctx=ctx)[0]
+    R0, R1 = _log_mean_exp(track[0]), _log_mean_exp(lam1)
+    info = {"scores": ss[:m].copy(), "track": track[:m + 1].copy(), "m": cm[:m].astype(np.int64),
+            "nconv_min": int(ncm.value), "refreshes": int(nrf.value), "R0": R0, "R1": R1,
+            "rob_score": (R1 - R0) * 100.0 / R0 if R0 != 0.0 else 0.0, "D": D}
+    return edges, info
+
+
 def find_top_edges_miobi(A, num, t=25, tol=0.0, max_spmm=0, seed=0, ctx: Optional[Context] = None):
     """The top `num` existing edges ranked by ascending MIOBI score (the edge
     MIOBI would remove first comes first) from the leading t eigenpairs of

@@ -512,6 +512,47 @@ int kt_miobi_make(kt_matrix_t A, int k, int t, int refresh, double tol, int max_
                   int64_t* sel_i, int64_t* sel_j, double* sel_score, double* lambda_track,
                   int* cand_m, int64_t* nsel, int* nconv_min, int* refreshes);
 
+/* The MIOBI node score from t eigenpairs on the rows of A (MIOBIBreakNode.m:
+ * 186-202): score[r] = sum_{k < t} exp(lambda[k]) exp(-2 V[r, k] W[r, k]) with
+ * W[r, .] the sum of the rows of V over the neighbours of r; +Inf for a node
+ * without a neighbour.  lambda (t), V (n x t column-major, used as given) and
+ * score (n) are host arrays; 1 <= t <= 32.  A row's neighbours and the t terms
+ * are added in a fixed order: the same arguments give the same bits.  Errors
+ * as kt_miobi_break_node's, without k and shift. */
+int kt_nodes_score_topk(kt_matrix_t A, int t, const double* lambda, const double* V, double* score);
+
+/* MIOBI's top-t node removal (MIOBIBreakNode.m's second loop, with t and the
+ * recomputation threshold parameters) with the step loop on the device: k
+ * times, score every node that still has a neighbour with the leading t
+ * eigenpairs (kt_eigs_topk with tol, max_spmm, seed; column 0 of V taken by
+ * absolute value), remove the node with the smallest score (exactly equal
+ * scores: the smaller index) -- its row and column are cleared -- and shift
+ * the eigenvalues.  shift 0 (`reference`): lambda_k -= 2 V[r, k] s_k -
+ * V[r, k]^2 with s_k the sum of column k over ALL n rows, which is what the
+ * reference's deltaA (the whole row and column at -1, :216-217) gives; shift 1
+ * (`first_order`): lambda_k -= 2 V[r, k] W[r, k] over the entries actually
+ * removed.  The vectors stay as computed between two recomputations, which is
+ * what the reference's update amounts to.  Every step
+ * adds 2 deg(r) to a count of removed entries; refresh > 0: once the count
+ * reaches refresh it is taken mod refresh and, unless the step was the last,
+ * the eigenpairs are recomputed on the edited matrix (the reference uses 50);
+ * refresh <= 0: never.  The steps between two recomputations are queued
+ * without a host synchronisation; the device ends the window.  A must hold
+ * unit weights and a zero diagonal; it is edited in place.
+ * Outputs: sel (0-based), sel_score and sel_deg (the node's degree when it
+ * was removed), k each; lambda_track (nullable), (k + 1) x t ROW-major: row s
+ * = the eigenvalues that score step s + 1 (a recomputation replaces its step's
+ * row); *nsel < k once no node has a neighbour; *nconv_min (nullable) the
+ * smallest nconv a kt_eigs_topk run returned; *refreshes (nullable) the
+ * recomputations.  The same arguments give the same bits.  KT_ERR_ARG before
+ * the device is touched for NULL arguments, k < 0, t outside 2..min(32, n), a
+ * shift other than 0 / 1, a matrix that is not unit-weight or has a diagonal
+ * entry, or outstanding kt_slq_submit calls; KT_ERR_NOT_HERMITIAN for
+ * non-symmetric A.  On any error A is left as it was. */
+int kt_miobi_break_node(kt_matrix_t A, int k, int t, int refresh, int shift, double tol, int max_spmm,
+                        uint64_t seed, int64_t* sel, double* sel_score, int64_t* sel_deg,
+                        double* lambda_track, int64_t* nsel, int* nconv_min, int* refreshes);
+
 /* Per-kernel timing (HIP events recorded on the library's stream around each
  * launch of the named kernel while enabled).  kernel: 0 = the probe-Lanczos
  * gather pass (k_spmm_lanczos in the y-form sweep, k_spmm_dot = K1 in the
@@ -535,7 +576,10 @@ int kt_miobi_make(kt_matrix_t A, int k, int t, int refresh, double tol, int max_
  * k_miobi_pick and, in mode 1, the rotation and normalisation), and
  * kt_pairs_score_topk's scoring launch,
  * 12 = kt_miobi_make's steps, one interval per step (k_miobi_make_score,
- * k_miobi_make_pick).
+ * k_miobi_make_pick),
+ * 13 = kt_miobi_break_node's steps, one interval per step (k_miobi_node_score,
+ * k_miobi_node_pick; a step queued past its window's end is a pair of no-op
+ * launches), and kt_nodes_score_topk's scoring launch.
  * Returns launch count and summed milliseconds. */
 int kt_profile_enable(kt_context_t ctx, int enable);
 int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* total_ms);
@@ -573,9 +617,10 @@ int kt_debug_delay(kt_context_t ctx, int lane, double microseconds);
  * kt_slq_trace_auto calls (those queued past a sweep's last stop, which
  * return at once, included), since context creation.  stat 9: thick restarts
  * of kt_eigs_topk calls, since context creation.  stats 10, 11, 12: host
- * microseconds of the last kt_miobi_make call on this context -- its
- * eigensolver runs; its candidate ranking, mask construction and uploads; its
- * edits of A. */
+ * microseconds of the last kt_miobi_make or kt_miobi_break_node call on this
+ * context -- its eigensolver runs; its candidate ranking, mask construction
+ * and uploads (kt_miobi_break_node: staging V, the eigenvalues and the window's
+ * row lists); its edits of A. */
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value);
 
 /* Threads of the process-wide host pool (the per-column / per-candidate

@@ -17,9 +17,9 @@ from .core import (Context, DeviceMatrix, DiagEstimate, EntryEstimate, default_c
                    slq_trace_auto, trace_exp,
                    trace_fun_update)
 from .greedy import (compute_centrality, default_greedy_tol, edge2low_rank, find_top_edges,
-                     find_top_edges_fun, find_top_edges_miobi, find_top_missing_edges, greedy_krylov, krylov_miobi,
-                     krylov_miobi_sharded, miobi_break, miobi_loop, miobi_make, pairs_score_topk, select_extreme,
-                     trace_fun_update_pairs)
+                     find_top_edges_fun, find_top_edges_miobi, find_top_missing_edges, find_top_nodes_miobi,
+                     greedy_krylov, krylov_miobi, krylov_miobi_sharded, miobi_break, miobi_break_node, miobi_loop,
+                     miobi_make, nodes_score_topk, pairs_score_topk, select_extreme, trace_fun_update_pairs)
 from . import datasets, matv73
 from .dist import mc_trace_sharded, trace_exp_sharded
 from .datasets import load_problem, load_unweighted, prepare_unweighted, prepare_weighted
@@ -36,5 +36,5 @@ __all__ = [
     "natural_connectivity_topk", "datasets", "matv73",
     "load_problem", "load_unweighted", "prepare_unweighted", "prepare_weighted",
     "mc_trace_sharded", "trace_exp_sharded", "edge2low_rank", "pairs_score_topk", "miobi_break", "miobi_make",
-    "find_top_edges_miobi",
+    "find_top_edges_miobi", "miobi_break_node", "nodes_score_topk", "find_top_nodes_miobi",
 ]

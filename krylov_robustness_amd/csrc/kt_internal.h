@@ -143,11 +143,13 @@ struct ProfSlot {
 // PROF_MIOBI: one interval per kt_miobi_break step (k_miobi_score, k_miobi_pick
 // and, in `paper` mode, the rotation and normalisation) and per
 // kt_pairs_score_topk scoring launch.  PROF_MIOBI_MAKE: one interval per
-// kt_miobi_make step (k_miobi_make_score, k_miobi_make_pick)
+// kt_miobi_make step (k_miobi_make_score, k_miobi_make_pick).  PROF_MIOBI_NODE:
+// one interval per kt_miobi_break_node step (k_miobi_node_score,
+// k_miobi_node_pick) and per kt_nodes_score_topk scoring launch
 enum {
     PROF_SPMM = 0, PROF_UPDATE = 1, PROF_START = 2, PROF_YBLOCK = 3, PROF_EXPMV = 4, PROF_FIRST = 5,
     PROF_CHECK = 6, PROF_DIAG = 7, PROF_DIAG_START = 8, PROF_ENTRIES = 9, PROF_EIGS = 10, PROF_MIOBI = 11,
-    PROF_MIOBI_MAKE = 12, PROF_NSLOTS = 13
+    PROF_MIOBI_MAKE = 12, PROF_MIOBI_NODE = 13, PROF_NSLOTS = 14
 };
 
 // Buffers of one probe-sweep lane (kt_slq.cpp); two lanes let two sweeps
@@ -265,8 +267,9 @@ struct kt_context_s {
     int64_t int0_sweeps = 0;      // y-form sweeps that carried y_0 as int16 row sums (kt_slq.h int0_applies)
     int64_t auto_passes = 0;      // y-form step passes queued by kt_slq_trace_auto calls (gated ones included)
     int64_t eigs_restarts = 0;    // thick restarts of kt_eigs_topk calls
-    // host microseconds of the last kt_miobi_make call: its eigensolver runs; its
-    // candidate ranking, mask construction and uploads; its set_pairs edits
+    // host microseconds of the last kt_miobi_make or kt_miobi_break_node call:
+    // its eigensolver runs; its candidate ranking, mask construction and uploads
+    // (break_node: staging V, e and the window's row lists); its edits of A
     int64_t make_eig_us = 0, make_rank_us = 0, make_edit_us = 0;
     int ky_flags = 8;   // y-form pass flags (8 = nontemporal store of y_{j+1}, +0.3 %)
     bool yform = true;  // KT_SLQ_YFORM=0: the hot path runs the explicit K1/K2 sweep

@@ -289,6 +289,33 @@ hipError_t launch_miobi_make_pick(int nparts, const double* part_s, const unsign
                                   const int* node, double* e, double* c, unsigned long long* mask, int* deg,
                                   int* sel_i, int* sel_j, double* sel_score, double* track, int* cand_m,
                                   int* state, hipStream_t st);
+// MIOBI break-node (kt_miobi_break_node).  V as above; (rowptr,
+// col): the natural-order CSR of a unit-weight matrix with a zero diagonal;
+// alive: one byte per node; long_rows: the n_long rows longer than
+// kMiobiNodeLong, in any order; state = {steps, stop, acc, window end}.
+// launch_miobi_node_score: score[r] = sum_{k < t} c[k] exp(-2 V[r, k] W[r, k]),
+// W[r, .] the sum of the live neighbours' rows; +Inf for a dead row or one with
+// no live neighbour; nblocks = miobi_node_blocks(n, max_blocks) workgroups each
+// leave their first candidate (smallest score, exactly equal scores by the
+// smaller node; node -1: none) and its live degree in part_*[b]; score
+// (nullable, n doubles) receives every row's score.  launch_miobi_node_pick
+// reduces the candidates and applies the step (see the kernel); shift 0 reads
+// colsum (launch_miobi_colsum: s[k] = sum_r V[r, k], part: kMiobiLd
+// miobi_norm_blocks(n) doubles), shift 1 gathers the node's row again.  A set
+// state[1] or state[3] makes the score and pick launches a no-op.
+constexpr int kMiobiNodeBatch = 8;    // row reads a half-wave issues before the first add
+constexpr int kMiobiNodeLong = 128;   // a longer row is split over a workgroup
+constexpr int kMiobiNodeChunk = 64;   // entries of a split row per half-wave and trip (8 x 64 per workgroup trip)
+int miobi_node_blocks(int64_t n, int max_blocks);
+hipError_t launch_miobi_node_score(int64_t n, int t, const double* V, const double* c, const int* rowptr,
+                                   const int* col, const unsigned char* alive, const int* long_rows, int n_long,
+                                   double* score, int nblocks, double* part_s, int* part_node, int* part_deg,
+                                   const int* state, hipStream_t st);
+hipError_t launch_miobi_node_pick(int nparts, const double* part_s, const int* part_node, const int* part_deg, int t,
+                                  int shift, int refresh, const double* V, const int* rowptr, const int* col,
+                                  unsigned char* alive, double* e, double* c, const double* colsum, int* sel_node,
+                                  double* sel_score, int* sel_deg, double* track, int* state, hipStream_t st);
+hipError_t launch_miobi_colsum(int64_t n, const double* V, double* part, double* s, hipStream_t st);
 int inf_norm_blocks();
 // normest1 (t = 1) reductions, normest1_blocks(n) partials each: sum |Y| in
 // partial[0, nb), S_prev . S in partial[nb, 2 nb), S = mysign(Y); per-block

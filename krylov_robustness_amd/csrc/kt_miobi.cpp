@@ -1,7 +1,9 @@
 // kt_miobi.cpp -- kt_miobi_break and kt_pairs_score_topk: MIOBI's top-t edge
 // removal (MIOBIBreakEdge2.m / MIOBIBreakEdge2_weighted.m) with the step loop
 // on the device (kernels in kt_miobi.hip); and kt_miobi_make,
-// its edge addition (MIOBIMakeEdge.m), at the end of the file.
+// its edge addition (MIOBIMakeEdge.m), and kt_miobi_break_node
+// with kt_nodes_score_topk, its node removal (MIOBIBreakNode.m; §4.2g), at the
+// end of the file.
 //
 // A window is the run of steps between two eigenpair recomputations.  Its
 // steps are queued back to back -- per step k_miobi_score over the pair list
@@ -14,6 +16,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "kt_block.h"
@@ -398,6 +401,199 @@ void miobi_make_impl(kt_matrix_s* A, int k, int t, int refresh, double tol, int 
     if (refreshes) *refreshes = nref;
 }
 
+// the window's long-row list (rows longer than kMiobiNodeLong) on the device
+int upload_long_rows(kt_matrix_s* A, int* dLr, std::vector<int>& rows) {
+    miobi_long_rows(A->n, A->h_rowptr.data(), kMiobiNodeLong, rows);
+    if (!rows.empty()) {
+        KT_HIP(hipMemcpyAsync(dLr, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice, A->ctx->stream));
+        KT_HIP(hipStreamSynchronize(A->ctx->stream));
+    }
+    return (int)rows.size();
+}
+
+// kt_miobi_break_node past its argument checks (MIOBIBreakNode.m:176-297 with t
+// and the threshold parameters).  Per window (the steps between two eigenpair
+// recomputations): the eigenpairs go up, the column sums of V are formed
+// (shift 0), and min(remaining, ceil(refresh / 2)) steps (k_miobi_node_score,
+// k_miobi_node_pick) are queued back to back -- the device ends the window
+// itself once the removed-entry count reaches `refresh`, and the launches
+// queued past that point return at once.  Selections, scores, degrees, track
+// rows and the state come back once; the host replays the count, clears the
+// removed nodes' rows and columns in one pass over its CSR and drops the device
+// copies.  edited: the host CSR was changed (the caller restores it on an error).
+void miobi_break_node_impl(kt_matrix_s* A, int k, int t, int refresh, int shift, double tol, int max_spmm,
+                           uint64_t seed, int64_t* sel, double* sel_score, int64_t* sel_deg, double* track,
+                           int64_t* nsel, int* nconv_min, int* refreshes, bool& edited) {
+    kt_context_s* ctx = A->ctx;
+    const int64_t n = A->n;
+    *nsel = 0;
+    if (nconv_min) *nconv_min = t;
+    if (refreshes) *refreshes = 0;
+    if (track) std::fill(track, track + (size_t)(k + 1) * t, 0.0);
+    if (A->nnz == 0) return;  // every node is isolated: nothing scores below +Inf
+
+    KT_HIP(hipSetDevice(ctx->device));
+    prof_recycle(ctx);
+    ctx->make_eig_us = ctx->make_rank_us = ctx->make_edit_us = 0;
+    auto mark = std::chrono::steady_clock::now();
+    const auto lap = [&mark](int64_t& into) {
+        const auto now = std::chrono::steady_clock::now();
+        into += std::chrono::duration_cast<std::chrono::microseconds>(now - mark).count();
+        mark = now;
+    };
+    std::vector<double> lam(t), Vh((size_t)n * t), stage;
+    int nconv = 0, nc_min;
+    eigs_topk_impl(A, t, tol, max_spmm, seed, lam.data(), Vh.data(), nullptr, &nconv, nullptr);
+    lap(ctx->make_eig_us);
+    nc_min = nconv;
+    if (track) std::copy(lam.begin(), lam.end(), track);
+
+    std::vector<int> long_rows;
+    miobi_long_rows(n, A->h_rowptr.data(), kMiobiNodeLong, long_rows);  // rows only shrink: the most there will be
+    const int nblocks = miobi_node_blocks(n, 0);
+    const int kk = std::max(k, 1);
+    DevMat dV;
+    dV.alloc(ctx, n, kLd, false);
+    Carver cv;
+    const size_t oE = cv.take(sizeof(double) * kLd), oC = cv.take(sizeof(double) * kLd),
+                 oS = cv.take(sizeof(double) * kLd), oNp = cv.take(sizeof(double) * kLd * miobi_norm_blocks(n)),
+                 oPs = cv.take(sizeof(double) * kMiobiMaxBlocks), oPn = cv.take(sizeof(int) * kMiobiMaxBlocks),
+                 oPd = cv.take(sizeof(int) * kMiobiMaxBlocks), oSt = cv.take(sizeof(int) * 4),
+                 oSn = cv.take(sizeof(int) * kk), oSs = cv.take(sizeof(double) * kk),
+                 oSd = cv.take(sizeof(int) * kk), oTr = cv.take(sizeof(double) * kLd * (kk + 1)),
+                 oLr = cv.take(sizeof(int) * std::max<size_t>(long_rows.size(), 1)), oAl = cv.take((size_t)n);
+    Block blk;
+    blk.alloc(ctx, cv.bytes);
+    double *dE = blk.at<double>(oE), *dC = blk.at<double>(oC), *dS = blk.at<double>(oS), *dNp = blk.at<double>(oNp);
+    double *dPs = blk.at<double>(oPs), *dSs = blk.at<double>(oSs), *dTr = blk.at<double>(oTr);
+    int *dPn = blk.at<int>(oPn), *dPd = blk.at<int>(oPd), *dSt = blk.at<int>(oSt), *dSn = blk.at<int>(oSn);
+    int *dSd = blk.at<int>(oSd), *dLr = blk.at<int>(oLr);
+    unsigned char* dAl = blk.at<unsigned char>(oAl);
+    hipStream_t st = ctx->stream;
+    KT_HIP(hipMemsetAsync(dAl, 1, (size_t)n, st));
+    KT_HIP(hipMemsetAsync(dTr, 0, sizeof(double) * kLd * (kk + 1), st));
+    KT_HIP(hipStreamSynchronize(st));
+
+    std::vector<int> hsn(kk), hsd(kk);
+    std::vector<double> hss(kk), htr((size_t)kLd * (kk + 1));
+    std::vector<unsigned char> dead((size_t)n, 0);
+    int done = 0, nref = 0, hacc = 0;
+    while (done < k) {
+        const int w = miobi_node_window(k - done, refresh);
+        mark = std::chrono::steady_clock::now();
+        const DevCSR& M = natural_csr(A);  // the edited matrix's copy
+        const int n_long = upload_long_rows(A, dLr, long_rows);
+        int state[4] = {done, 0, hacc, 0};
+        KT_HIP(hipMemcpyAsync(dSt, state, sizeof state, hipMemcpyHostToDevice, st));
+        upload_v(ctx, n, t, Vh.data(), true, dV.col(0), stage);  // :177  column 0 by absolute value
+        upload_e(ctx, t, lam.data(), dE, dC);
+        if (shift == 0) KT_HIP(launch_miobi_colsum(n, dV.col(0), dNp, dS, st));
+        lap(ctx->make_rank_us);
+        for (int s = 0; s < w; ++s) {
+            prof_begin(ctx, PROF_MIOBI_NODE, st, t);
+            KT_HIP(launch_miobi_node_score(n, t, dV.col(0), dC, M.rowptr, M.col, dAl, dLr, n_long, nullptr, nblocks,
+                                           dPs, dPn, dPd, dSt, st));
+            KT_HIP(launch_miobi_node_pick(nblocks, dPs, dPn, dPd, t, shift, refresh, dV.col(0), M.rowptr, M.col, dAl,
+                                          dE, dC, dS, dSn, dSs, dSd, dTr, dSt, st));
+            prof_end(ctx, PROF_MIOBI_NODE, st);
+        }
+        KT_HIP(hipMemcpyAsync(state, dSt, sizeof state, hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(hsn.data() + done, dSn + done, sizeof(int) * w, hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(hsd.data() + done, dSd + done, sizeof(int) * w, hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(hss.data() + done, dSs + done, sizeof(double) * w, hipMemcpyDeviceToHost, st));
+        KT_HIP(hipMemcpyAsync(htr.data() + (size_t)kLd * (done + 1), dTr + (size_t)kLd * (done + 1),
+                              sizeof(double) * kLd * w, hipMemcpyDeviceToHost, st));
+        KT_HIP(hipStreamSynchronize(st));
+        const int now = state[0];
+        if (now < done || now > done + w)
+            fail(KT_ERR_HIP, "kt_miobi_break_node: the device step count is out of range");
+        bool ended = false;
+        for (int s = done; s < now; ++s) {
+            const int r = hsn[s], d = hsd[s];
+            if (r < 0 || r >= n || dead[(size_t)r] || d < 1 || d > A->h_rowptr[r + 1] - A->h_rowptr[r] || ended)
+                fail(KT_ERR_HIP, "kt_miobi_break_node: the device's selection record is inconsistent");
+            ended = miobi_node_book(hacc, d, refresh);
+            dead[(size_t)r] = 1;
+            sel[s] = r;
+            sel_score[s] = hss[s];
+            sel_deg[s] = d;
+            if (track) std::copy(htr.begin() + (size_t)kLd * (s + 1), htr.begin() + (size_t)kLd * (s + 1) + t,
+                                 track + (size_t)(s + 1) * t);
+        }
+        if ((refresh > 0 && state[2] != hacc) || (state[3] != 0) != ended)
+            fail(KT_ERR_HIP, "kt_miobi_break_node: the device's removed-entry count differs from the host's");
+        if (now > done) {  // :211-212 for the window's nodes
+            mark = std::chrono::steady_clock::now();
+            edited = true;
+            miobi_clear_nodes(n, dead, A->h_rowptr, A->h_col, A->h_val);
+            A->nnz = (int64_t)A->h_col.size();
+            refresh_device(A);
+            lap(ctx->make_edit_us);
+        }
+        done = now;
+        *nsel = done;
+        if (state[1] || done >= k || A->nnz == 0) break;  // (an empty matrix has nothing left to score)
+        if (!ended) fail(KT_ERR_HIP, "kt_miobi_break_node: a full window did not reach its end");
+        // :286-295  the eigenpairs of the edited matrix
+        mark = std::chrono::steady_clock::now();
+        eigs_topk_impl(A, t, tol, max_spmm, seed, lam.data(), Vh.data(), nullptr, &nconv, nullptr);
+        lap(ctx->make_eig_us);
+        nc_min = std::min(nc_min, nconv);
+        ++nref;
+        if (track) std::copy(lam.begin(), lam.end(), track + (size_t)done * t);
+    }
+    if (nconv_min) *nconv_min = nc_min;
+    if (refreshes) *refreshes = nref;
+}
+
+void nodes_score_impl(kt_matrix_s* A, int t, const double* lambda, const double* V, double* score) {
+    kt_context_s* ctx = A->ctx;
+    const int64_t n = A->n;
+    KT_HIP(hipSetDevice(ctx->device));
+    prof_recycle(ctx);
+    const DevCSR& M = natural_csr(A);
+    std::vector<int> long_rows;
+    miobi_long_rows(n, A->h_rowptr.data(), kMiobiNodeLong, long_rows);
+    const int nblocks = miobi_node_blocks(n, 0);
+    DevMat dV;
+    dV.alloc(ctx, n, kLd, false);
+    Carver cv;
+    const size_t oE = cv.take(sizeof(double) * kLd), oC = cv.take(sizeof(double) * kLd),
+                 oPs = cv.take(sizeof(double) * kMiobiMaxBlocks), oPn = cv.take(sizeof(int) * kMiobiMaxBlocks),
+                 oPd = cv.take(sizeof(int) * kMiobiMaxBlocks), oSc = cv.take(sizeof(double) * n),
+                 oLr = cv.take(sizeof(int) * std::max<size_t>(long_rows.size(), 1)), oAl = cv.take((size_t)n);
+    Block blk;
+    blk.alloc(ctx, cv.bytes);
+    hipStream_t st = ctx->stream;
+    std::vector<double> stage;
+    KT_HIP(hipMemsetAsync(blk.at<unsigned char>(oAl), 1, (size_t)n, st));
+    const int n_long = upload_long_rows(A, blk.at<int>(oLr), long_rows);
+    upload_v(ctx, n, t, V, false, dV.col(0), stage);
+    upload_e(ctx, t, lambda, blk.at<double>(oE), blk.at<double>(oC));
+    prof_begin(ctx, PROF_MIOBI_NODE, st, t);
+    KT_HIP(launch_miobi_node_score(n, t, dV.col(0), blk.at<double>(oC), M.rowptr, M.col, blk.at<unsigned char>(oAl),
+                                   blk.at<int>(oLr), n_long, blk.at<double>(oSc), nblocks, blk.at<double>(oPs),
+                                   blk.at<int>(oPn), blk.at<int>(oPd), nullptr, st));
+    prof_end(ctx, PROF_MIOBI_NODE, st);
+    KT_HIP(hipMemcpyAsync(score, blk.at<double>(oSc), sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    KT_HIP(hipStreamSynchronize(st));
+}
+
+// what both node entries require of A (MIOBIBreakNode.m:31-39 binarises its
+// input; its datasets have no self-loop)
+void node_matrix_checks(kt_matrix_s* A, const char* who) {
+    const std::string w(who);
+    if (A->n > INT32_MAX) fail(KT_ERR_ARG, (w + ": n must fit 32-bit indices").c_str());
+    if (A->nnz > 0 && !A->unit_values)
+        fail(KT_ERR_ARG, (w + ": the matrix must be a unit-weight adjacency matrix (MIOBIBreakNode.m binarises "
+                              "its input)").c_str());
+    if (miobi_has_diagonal(A->n, A->h_rowptr.data(), A->h_col.data()))
+        fail(KT_ERR_ARG, (w + ": the matrix must have a zero diagonal").c_str());
+    if (A->ctx->ws.slq_submitted != A->ctx->ws.slq_collected)
+        fail(KT_ERR_ARG, (w + ": kt_slq_submit calls are outstanding on this context").c_str());
+    require_symmetric(A, "MIOBI:: adjacency matrix has to be symmetric");
+}
+
 }  // namespace
 
 }  // namespace kt
@@ -477,6 +673,52 @@ extern "C" int kt_miobi_make(kt_matrix_t A, int k, int t, int refresh, double to
                     set_pairs(A, (int64_t)added_i.size(), added_i.data(), added_j.data(), 0.0);
                 } catch (...) {
                 }
+                *nsel = 0;
+            }
+            throw;
+        }
+    }
+    KT_MIOBI_GUARD_END
+}
+
+extern "C" int kt_nodes_score_topk(kt_matrix_t A, int t, const double* lambda, const double* V, double* score) {
+    try {
+        if (!A || !lambda || !V || !score) fail(KT_ERR_ARG, "kt_nodes_score_topk: NULL argument");
+        if (t < 1 || t > kMiobiLd) fail(KT_ERR_ARG, "kt_nodes_score_topk: t must be in [1, 32]");
+        node_matrix_checks(A, "kt_nodes_score_topk");
+        nodes_score_impl(A, t, lambda, V, score);
+    }
+    KT_MIOBI_GUARD_END
+}
+
+extern "C" int kt_miobi_break_node(kt_matrix_t A, int k, int t, int refresh, int shift, double tol, int max_spmm,
+                                   uint64_t seed, int64_t* sel, double* sel_score, int64_t* sel_deg,
+                                   double* lambda_track, int64_t* nsel, int* nconv_min, int* refreshes) {
+    std::vector<int64_t> rowptr0;
+    std::vector<int32_t> col0;
+    bool edited = false;
+    try {
+        try {
+            if (!A || !nsel || (k > 0 && (!sel || !sel_score || !sel_deg)))
+                fail(KT_ERR_ARG, "kt_miobi_break_node: NULL argument");
+            if (k < 0) fail(KT_ERR_ARG, "kt_miobi_break_node: k must not be negative");
+            if (t < 2 || t > kMiobiLd || t > A->n)
+                fail(KT_ERR_ARG, "kt_miobi_break_node: t must be in [2, min(32, n)]");
+            if (shift != 0 && shift != 1)
+                fail(KT_ERR_ARG, "kt_miobi_break_node: shift must be 0 (reference) or 1 (first_order)");
+            node_matrix_checks(A, "kt_miobi_break_node");
+            rowptr0 = A->h_rowptr;  // unit weights: the pattern is the matrix
+            col0 = A->h_col;
+            miobi_break_node_impl(A, k, t, refresh, shift, tol, max_spmm, seed, sel, sel_score, sel_deg, lambda_track,
+                                  nsel, nconv_min, refreshes, edited);
+        } catch (...) {
+            // on any error the matrix stays as it was
+            if (edited) {
+                A->h_rowptr = rowptr0;
+                A->h_col = col0;
+                A->h_val.assign(col0.size(), 1.0);
+                A->nnz = (int64_t)col0.size();
+                refresh_device(A);
                 *nsel = 0;
             }
             throw;

@@ -3,7 +3,9 @@
 // eigenpairs on a pair list, the global argmin with the step applied on the
 // device, and the column normalisation of the `paper` eigenvector update; and,
 // at the end of the file, the two kernels of kt_miobi_make (§4.2f): the scores
-// of a dense block of candidate pairs from LDS tiles, and its argmax and step.
+// of a dense block of candidate pairs from LDS tiles, and its argmax and step;
+// and the three of kt_miobi_break_node (§4.2g): the node score as a CSR row
+// pass over V, its argmin and step, and V's column sums.
 //
 // V is n x 32 row-major in ORIGINAL numbering (t <= 32 live columns, the rest
 // zero): one row is 256 bytes, so a half-wave with lane = column reads a row
@@ -569,6 +571,339 @@ hipError_t launch_miobi_make_pick(int nparts, const double* part_s, const unsign
         return hipErrorInvalidValue;
     k_miobi_make_pick<<<1, 256, 0, st>>>(nparts, part_s, part_key, part_ok, mcap, t, k, n, W, node, e, c, mask, deg,
                                          sel_i, sel_j, sel_score, track, cand_m, state);
+    return hipGetLastError();
+}
+
+// ---- break-node (kt_miobi_break_node, MIOBIBreakNode.m) ----
+
+namespace {
+
+constexpr int kNB = kMiobiNodeBatch;
+constexpr int kNodeTrip = kHalves * kMiobiNodeChunk;  // entries of a split row a workgroup takes per trip
+
+// (s1, i1) before (s2, i2): the smaller score, exactly equal scores by the
+// smaller node index -- the first minimum of [~, minIndex] = min(score)
+// (MIOBIBreakNode.m:204).  i < 0: no candidate.  A NaN score loses to every number.
+__device__ __forceinline__ bool node_before(double s1, int i1, double s2, int i2) {
+    if (i1 < 0) return false;
+    if (i2 < 0) return true;
+    if (s1 != s2) return s1 < s2 || (s2 != s2 && s1 == s1);
+    return i1 < i2;
+}
+
+// w += V[col[j], k] over the entries j of [beg, end) (beg < end) whose node is
+// alive, j ascending; cnt += their number.  kNB row reads are issued before the
+// first add; the loads are unconditional (an index past the end is clamped to
+// the last entry, a dead node's row is read and dropped), so none waits for a
+// branch.
+__device__ __forceinline__ void node_gather(const double* __restrict__ V, const int* __restrict__ col,
+                                            const unsigned char* __restrict__ alive, int beg, int end, int k,
+                                            double& w, int& cnt) {
+    for (int j = beg; j < end; j += kNB) {
+        double x[kNB];
+        bool on[kNB];
+#pragma unroll
+        for (int u = 0; u < kNB; ++u) {
+            const int cidx = col[min(j + u, end - 1)];
+            on[u] = j + u < end && alive[cidx] != 0;
+            x[u] = V[(int64_t)cidx * kLd + k];
+        }
+#pragma unroll
+        for (int u = 0; u < kNB; ++u) {
+            w += on[u] ? x[u] : 0.0;
+            cnt += on[u] ? 1 : 0;
+        }
+    }
+}
+
+// half-wave h's share of the split row [beg, end): the chunks of
+// kMiobiNodeChunk entries numbered h, h + 8, h + 16, ..., ascending
+__device__ __forceinline__ void node_gather_split(const double* __restrict__ V, const int* __restrict__ col,
+                                                  const unsigned char* __restrict__ alive, int beg, int end, int h,
+                                                  int k, double& w, int& cnt) {
+    for (int64_t c0 = (int64_t)beg + (int64_t)h * kMiobiNodeChunk; c0 < end; c0 += kNodeTrip)
+        node_gather(V, col, alive, (int)c0, (int)min(c0 + kMiobiNodeChunk, (int64_t)end), k, w, cnt);
+}
+
+__device__ __forceinline__ double pos_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
+
+}  // namespace
+
+// The node score of MIOBIBreakNode.m:186-202 on the CSR (rowptr, col; unit
+// weights, zero diagonal) of the window's matrix, with alive[] the nodes not
+// yet removed in it: for a live row r
+//   W[r, k] = sum_{j in row r, alive[col j]} V[col j, k]     (j ascending)
+//   score[r] = sum_{k < t} c[k] exp(-2 V[r, k] W[r, k])
+// with lane = k and the t terms added by the xor butterfly 16, 8, 4, 2, 1.  A
+// dead row, and a row with no live neighbour, scores +Inf and is no candidate.
+// Rows of at most kMiobiNodeLong entries: one half-wave per row, workgroup b
+// takes rows 8 b + h + 8 gridDim.x q.  Longer rows (long_rows, n_long of them,
+// every row longer than kMiobiNodeLong and no other): one workgroup per row,
+// half-wave h the chunks h, h + 8, ... of kMiobiNodeChunk entries, the eight
+// partial sums added in the order h = 0..7.  A row's bits depend on V, c, t,
+// the row and alive only -- not on the grid.  score (nullable) receives every
+// row's score; part_*[blockIdx.x] the workgroup's first candidate under
+// node_before() and its live degree.  state (nullable): a set state[1] (stop)
+// or state[3] (window end) makes the launch a no-op.
+__global__ __launch_bounds__(256) void k_miobi_node_score(int n, int t, const double* __restrict__ V,
+                                                          const double* __restrict__ c,
+                                                          const int* __restrict__ rowptr,
+                                                          const int* __restrict__ col,
+                                                          const unsigned char* __restrict__ alive,
+                                                          const int* __restrict__ long_rows, int n_long,
+                                                          double* __restrict__ score, double* __restrict__ part_s,
+                                                          int* __restrict__ part_node, int* __restrict__ part_deg,
+                                                          const int* __restrict__ state) {
+    if (state && (state[1] || state[3])) return;  // the same words for every thread
+    __shared__ double sW[kHalves][kLd];
+    __shared__ int sN[kHalves];
+    __shared__ double red_s[kHalves];
+    __shared__ int red_i[kHalves], red_d[kHalves];
+    const int k = threadIdx.x & 31, h = threadIdx.x >> 5;
+    const double ck = k < t ? c[k] : 0.0;
+    const double inf = pos_inf();
+    double bs = 0.0;
+    int bi = -1, bd = 0;
+    for (int64_t rb = (int64_t)blockIdx.x * kHalves; rb < n; rb += (int64_t)gridDim.x * kHalves) {  // wave-uniform
+        const int64_t r = rb + h;
+        double w = 0.0, v = 0.0;
+        int cnt = 0;
+        bool own = false;
+        if (r < n) {
+            const int beg = rowptr[r], end = rowptr[r + 1];
+            own = end - beg <= kMiobiNodeLong;
+            if (own && end > beg && alive[r]) {
+                v = V[r * kLd + k];
+                node_gather(V, col, alive, beg, end, k, w, cnt);
+            }
+        }
+        double s = k < t ? ck * exp(-2.0 * (v * w)) : 0.0;
+        s += shfl_xor_d(s, 16);
+        s += shfl_xor_d(s, 8);
+        s += shfl_xor_d(s, 4);
+        s += shfl_xor_d(s, 2);
+        s += shfl_xor_d(s, 1);
+        if (own) {
+            if (cnt == 0) s = inf;
+            if (score && k == 0) score[r] = s;
+            if (s != inf && node_before(s, (int)r, bs, bi)) {
+                bs = s;
+                bi = (int)r;
+                bd = cnt;
+            }
+        }
+    }
+    for (int q = blockIdx.x; q < n_long; q += gridDim.x) {  // workgroup-uniform trip count
+        const int r = long_rows[q];
+        const int beg = rowptr[r], end = rowptr[r + 1];
+        const bool live = alive[r] != 0;
+        double w = 0.0;
+        int cnt = 0;
+        if (live) node_gather_split(V, col, alive, beg, end, h, k, w, cnt);
+        sW[h][k] = w;
+        if (k == 0) sN[h] = cnt;
+        __syncthreads();
+        w = 0.0;
+        cnt = 0;
+#pragma unroll
+        for (int g = 0; g < kHalves; ++g) {
+            w += sW[g][k];
+            cnt += sN[g];
+        }
+        __syncthreads();  // the next trip writes sW / sN again
+        const double v = live ? V[(int64_t)r * kLd + k] : 0.0;
+        double s = k < t ? ck * exp(-2.0 * (v * w)) : 0.0;
+        s += shfl_xor_d(s, 16);
+        s += shfl_xor_d(s, 8);
+        s += shfl_xor_d(s, 4);
+        s += shfl_xor_d(s, 2);
+        s += shfl_xor_d(s, 1);
+        if (cnt == 0) s = inf;
+        if (h == 0) {
+            if (score && k == 0) score[r] = s;
+            if (s != inf && node_before(s, r, bs, bi)) {
+                bs = s;
+                bi = r;
+                bd = cnt;
+            }
+        }
+    }
+    if (k == 0) {
+        red_s[h] = bs;
+        red_i[h] = bi;
+        red_d[h] = bd;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < kHalves; ++q)
+            if (node_before(red_s[q], red_i[q], bs, bi)) {
+                bs = red_s[q];
+                bi = red_i[q];
+                bd = red_d[q];
+            }
+        part_s[blockIdx.x] = bs;
+        part_node[blockIdx.x] = bi;
+        part_deg[blockIdx.x] = bd;
+    }
+}
+
+int miobi_node_blocks(int64_t n, int max_blocks) {
+    const int cap = max_blocks > 0 ? std::min(max_blocks, kMiobiMaxBlocks) : kMiobiMaxBlocks;
+    return (int)std::max<int64_t>(1, std::min<int64_t>((n + kHalves - 1) / kHalves, cap));
+}
+
+hipError_t launch_miobi_node_score(int64_t n, int t, const double* V, const double* c, const int* rowptr,
+                                   const int* col, const unsigned char* alive, const int* long_rows, int n_long,
+                                   double* score, int nblocks, double* part_s, int* part_node, int* part_deg,
+                                   const int* state, hipStream_t st) {
+    if (n < 1 || n > INT32_MAX || t < 1 || t > kLd || nblocks < 1 || nblocks > kMiobiMaxBlocks || n_long < 0 ||
+        n_long > n || (n_long > 0 && !long_rows))
+        return hipErrorInvalidValue;
+    k_miobi_node_score<<<nblocks, 256, 0, st>>>((int)n, t, V, c, rowptr, col, alive, long_rows, n_long, score, part_s,
+                                                part_node, part_deg, state);
+    return hipGetLastError();
+}
+
+// One workgroup: the minimum of the nparts workgroup candidates under
+// node_before(), then the step (MIOBIBreakNode.m:204-223, :283-295): with r the
+// node, d its live degree and s = state[0] the steps so far,
+//   sel_node[s] = r, sel_score[s] = its score, sel_deg[s] = d, alive[r] = 0,
+//   e[k] += dE[k], c[k] = exp(e[k]), track[(s + 1) 32 + k] = e[k]  (k < t),
+//   shift 0 (reference): dE[k] = -(2 V[r, k] colsum[k] - V[r, k]^2), the
+//     diagonal of V' deltaA V with deltaA's WHOLE row and column r at -1 (:216-217),
+//   shift 1 (first order): dE[k] = -2 V[r, k] W[r, k], W over the live
+//     neighbours of r, gathered here in the score kernel's order,
+//   state[2] = acc += 2 d (:208, :283); with refresh > 0 and acc >= refresh:
+//   acc %= refresh and state[3] = 1, the window's end (:286-292); refresh <= 0
+//   leaves state[2] alone;  state[0] = s + 1.
+// No candidate (every score +Inf): state[1] = 1 and nothing else.  A launch
+// that finds state[1] or state[3] set returns at once.
+__global__ __launch_bounds__(256) void k_miobi_node_pick(int nparts, const double* __restrict__ part_s,
+                                                         const int* __restrict__ part_node,
+                                                         const int* __restrict__ part_deg, int t, int shift,
+                                                         int refresh, const double* __restrict__ V,
+                                                         const int* __restrict__ rowptr,
+                                                         const int* __restrict__ col, unsigned char* alive,
+                                                         double* __restrict__ e, double* __restrict__ c,
+                                                         const double* __restrict__ colsum,
+                                                         int* __restrict__ sel_node, double* __restrict__ sel_score,
+                                                         int* __restrict__ sel_deg, double* __restrict__ track,
+                                                         int* __restrict__ state) {
+    if (state[1] || state[3]) return;
+    __shared__ double ss[256];
+    __shared__ int si[256], sd[256];
+    __shared__ double sW[kHalves][kLd];
+    const int tid = threadIdx.x, k = tid & 31, h = tid >> 5;
+    const int step = state[0], acc = state[2];
+    double bs = 0.0;
+    int bi = -1, bd = 0;
+    for (int q = tid; q < nparts; q += 256)
+        if (node_before(part_s[q], part_node[q], bs, bi)) {
+            bs = part_s[q];
+            bi = part_node[q];
+            bd = part_deg[q];
+        }
+    ss[tid] = bs;
+    si[tid] = bi;
+    sd[tid] = bd;
+    __syncthreads();  // every thread has read the state words
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w && node_before(ss[tid + w], si[tid + w], ss[tid], si[tid])) {
+            ss[tid] = ss[tid + w];
+            si[tid] = si[tid + w];
+            sd[tid] = sd[tid + w];
+        }
+        __syncthreads();
+    }
+    const int r = si[0], deg = sd[0];
+    if (r < 0) {
+        if (tid == 0) state[1] = 1;
+        return;
+    }
+    double w = 0.0;
+    if (shift) {  // the same value for every thread
+        const int beg = rowptr[r], end = rowptr[r + 1];
+        int cnt = 0;
+        if (end - beg > kMiobiNodeLong) node_gather_split(V, col, alive, beg, end, h, k, w, cnt);
+        else if (h == 0 && end > beg) node_gather(V, col, alive, beg, end, k, w, cnt);
+        sW[h][k] = w;
+        __syncthreads();  // the gathers have read alive[]
+        w = 0.0;
+#pragma unroll
+        for (int g = 0; g < kHalves; ++g) w += sW[g][k];
+    }
+    if (tid < t) {
+        const double v = V[(int64_t)r * kLd + tid];
+        const double de = shift ? -2.0 * (v * w) : -(2.0 * v * colsum[tid] - v * v);
+        const double en = e[tid] + de;
+        e[tid] = en;
+        c[tid] = exp(en);
+        track[(int64_t)(step + 1) * kLd + tid] = en;
+    }
+    if (tid == 0) {
+        sel_node[step] = r;
+        sel_score[step] = ss[0];
+        sel_deg[step] = deg;
+        alive[r] = 0;
+        if (refresh > 0) {
+            long long a = (long long)acc + 2LL * deg;
+            if (a >= refresh) {
+                a %= refresh;
+                state[3] = 1;
+            }
+            state[2] = (int)a;
+        }
+        state[0] = step + 1;
+    }
+}
+
+hipError_t launch_miobi_node_pick(int nparts, const double* part_s, const int* part_node, const int* part_deg, int t,
+                                  int shift, int refresh, const double* V, const int* rowptr, const int* col,
+                                  unsigned char* alive, double* e, double* c, const double* colsum, int* sel_node,
+                                  double* sel_score, int* sel_deg, double* track, int* state, hipStream_t st) {
+    if (nparts < 1 || nparts > kMiobiMaxBlocks || t < 1 || t > kLd || (shift != 0 && shift != 1) ||
+        (shift == 0 && !colsum))
+        return hipErrorInvalidValue;
+    k_miobi_node_pick<<<1, 256, 0, st>>>(nparts, part_s, part_node, part_deg, t, shift, refresh, V, rowptr, col, alive,
+                                         e, c, colsum, sel_node, sel_score, sel_deg, track, state);
+    return hipGetLastError();
+}
+
+// s[k] = sum_r V[r, k] over all n rows, in a fixed order (k_miobi_colsq's shape
+// without the square): workgroup b adds rows 8 b + (tid >> 5) + 8 gridDim.x q,
+// q ascending, per thread, then its eight row groups in ascending order;
+// k_miobi_colsum_fin adds the workgroups' partials in ascending order.
+__global__ __launch_bounds__(256) void k_miobi_colsum(int64_t n, const double* __restrict__ V,
+                                                      double* __restrict__ part) {
+    __shared__ double red[256];
+    const int k = threadIdx.x & 31, g = threadIdx.x >> 5;
+    double acc = 0.0;
+    for (int64_t r = (int64_t)blockIdx.x * 8 + g; r < n; r += (int64_t)gridDim.x * 8) acc += V[r * kLd + k];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x < kLd) {
+        double s = 0.0;
+        for (int q = 0; q < 8; ++q) s += red[q * 32 + threadIdx.x];
+        part[(size_t)blockIdx.x * kLd + threadIdx.x] = s;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_miobi_colsum_fin(int nparts, const double* __restrict__ part,
+                                                         double* __restrict__ s) {
+    if (threadIdx.x < kLd) {
+        double a = 0.0;
+        for (int q = 0; q < nparts; ++q) a += part[(size_t)q * kLd + threadIdx.x];
+        s[threadIdx.x] = a;
+    }
+}
+
+hipError_t launch_miobi_colsum(int64_t n, const double* V, double* part, double* s, hipStream_t st) {
+    if (n <= 0) return hipErrorInvalidValue;
+    const int nb = miobi_norm_blocks(n);
+    k_miobi_colsum<<<nb, 256, 0, st>>>(n, V, part);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    k_miobi_colsum_fin<<<1, 64, 0, st>>>(nb, part, s);
     return hipGetLastError();
 }
 

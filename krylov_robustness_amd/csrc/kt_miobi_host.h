@@ -1,8 +1,11 @@
 // kt_miobi_host.h -- the host-only parts of kt_miobi_make's driver
 // (kt_miobi.cpp): the candidate ranking, the adjacency
-// bitmask of the candidate block and the bookkeeping of the candidate count m.
-// Plain C++ with no device call, so that a stand-alone host program can run
-// them under a sanitizer (tests/native/miobi_make_check/host_san.cpp).
+// bitmask of the candidate block and the bookkeeping of the candidate count m;
+// and of kt_miobi_break_node's (§4.2g): the argument scan, the window length,
+// the removed-entry count replayed, the long-row list and the row / column
+// removal.  Plain C++ with no device call, so that a stand-alone host program
+// can run them under a sanitizer (tests/native/miobi_make_check/host_san.cpp,
+// tests/native/miobi_node_check/host_san.cpp).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -68,6 +71,63 @@ inline void miobi_build_mask(const int64_t* rowptr, const int32_t* col, const st
 inline int miobi_book_step(std::vector<int>& deg, int& maxdeg, int a, int b, int k, int64_t n) {
     maxdeg = std::max(maxdeg, std::max(++deg[(size_t)a], ++deg[(size_t)b]));
     return miobi_live_m(maxdeg, k, n);
+}
+
+// ---- break-node (kt_miobi_break_node, MIOBIBreakNode.m) --------------------
+
+// whether the CSR holds an entry (i, i)
+inline bool miobi_has_diagonal(int64_t n, const int64_t* rowptr, const int32_t* col) {
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t q = rowptr[i]; q < rowptr[i + 1]; ++q)
+            if (col[q] == i) return true;
+    return false;
+}
+
+// the steps to queue for one window: a selected node has degree >= 1 and so
+// adds at least 2 to the removed-entry count, which reaches `refresh` within
+// ceil(refresh / 2) steps (MIOBIBreakNode.m:208, :283-286); refresh <= 0: all
+inline int miobi_node_window(int remaining, int refresh) {
+    return refresh > 0 ? std::min(remaining, (refresh + 1) / 2) : remaining;
+}
+
+// the device's count replayed for one step: acc += 2 deg; at or beyond refresh
+// (> 0) the window ends and acc %= refresh (:283-292).  Returns whether it ends.
+inline bool miobi_node_book(int& acc, int deg, int refresh) {
+    if (refresh <= 0) return false;
+    const int64_t a = (int64_t)acc + 2 * (int64_t)deg;
+    acc = (int)(a >= refresh ? a % refresh : a);
+    return a >= refresh;
+}
+
+// the rows longer than thresh, ascending
+inline void miobi_long_rows(int64_t n, const int64_t* rowptr, int thresh, std::vector<int>& rows) {
+    rows.clear();
+    for (int64_t i = 0; i < n; ++i)
+        if (rowptr[i + 1] - rowptr[i] > thresh) rows.push_back((int)i);
+}
+
+// A(r, :) = 0, A(:, r) = 0 for every r with dead[r] (:211-212) in one pass over
+// the CSR; val may be empty (no values kept).  Returns the entries removed.
+inline int64_t miobi_clear_nodes(int64_t n, const std::vector<unsigned char>& dead, std::vector<int64_t>& rowptr,
+                                 std::vector<int32_t>& col, std::vector<double>& val) {
+    int64_t w = 0, beg = 0;
+    const bool vals = !val.empty();
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t end = rowptr[i + 1];
+        if (!dead[(size_t)i])
+            for (int64_t q = beg; q < end; ++q)
+                if (!dead[(size_t)col[q]]) {
+                    col[(size_t)w] = col[q];
+                    if (vals) val[(size_t)w] = val[q];
+                    ++w;
+                }
+        beg = end;
+        rowptr[i + 1] = w;
+    }
+    const int64_t removed = (int64_t)col.size() - w;
+    col.resize((size_t)w);
+    if (vals) val.resize((size_t)w);
+    return removed;
 }
 
 }  // namespace kt

@@ -531,6 +531,98 @@ def miobi_make(A, k, t=25, refresh=50, tol=0.0, max_spmm=0, seed=0, ctx: Optiona
     return edges, info
 
 
+def nodes_score_topk(A, lam, V, ctx: Optional[Context] = None):
+    """The MIOBI score of every node of A from t <= 32 eigenpairs: sum_k
+    exp(lam[k]) exp(-2 V[r, k] W[r, k]) with W[r, :] the sum of V's rows over
+    the neighbours of r, +Inf for a node without one (MIOBIBreakNode.m:186-202).
+    On the device (kt_nodes_score_topk); the neighbours and the t terms are
+    added in a fixed order.  A must hold unit weights and a zero diagonal; V is
+    used as given."""
+    from .core import _colmajor
+    D = _dev(A, ctx)
+    n, _ = D.info()
+    lam = np.ascontiguousarray(np.asarray(lam, dtype=np.float64).ravel())
+    Vc = _colmajor(V)
+    if Vc.shape != (n, lam.size):
+        raise ValueError(f"nodes_score_topk: V is {Vc.shape[0]} x {Vc.shape[1]}, expected {n} x {lam.size}")
+    score = np.zeros(max(n, 1))
+    _lib.check(_lib.load().kt_nodes_score_topk(D.handle, lam.size, _dptr(lam), _dptr(Vc), _dptr(score)))
+    return score[:n]
+
+
+def miobi_break_node(A, k, t=25, refresh=50, shift="reference", tol=0.0, max_spmm=0, seed=0,
+                     ctx: Optional[Context] = None):
+    """MIOBI's top-t node removal on the device (MIOBIBreakNode.m's second loop
+    with t a parameter; kt_miobi_break_node): k times, score every node that
+    still has a neighbour with the leading t eigenpairs, remove the
+    lowest-scoring one (its row and column are cleared) and shift the
+    eigenvalues.  shift "reference" is what the reference's code computes (its
+    deltaA sets the node's WHOLE row and column to -1), "first_order" the shift
+    for the entries actually removed.  Every step adds twice
+    the removed node's degree to a count; once the count reaches `refresh` (the
+    reference's 50) it is taken mod refresh and the eigenpairs are recomputed
+    (eigs_topk with tol, max_spmm, seed); never with refresh <= 0 (the
+    'NoUpdate' run).  The vectors stay as computed between recomputations.  A
+    must hold unit weights and a zero diagonal; a DeviceMatrix is edited in
+    place.
+
+    Returns (nodes, info): nodes 1-based, fewer than k once no node has a
+    neighbour; info: "scores", "degrees" (of each node when it was removed),
+    "track" (nsel + 1 rows of t eigenvalues: row s scores step s + 1),
+    "nconv_min", "refreshes", "R0" / "R1" = log(mean(exp(lam))) of
+    eigs_topk(., t) before and after, "rob_score" = (R0 - R1) 100 / R0
+    (:299-301), and "D" the edited DeviceMatrix."""
+    from .core import eigs_topk
+    if shift not in ("reference", "first_order"):
+        raise _lib.KrylovError(_lib.KT_ERR_ARG, "miobi_break_node: shift must be 'reference' or 'first_order'")
+    D = _dev(A, ctx)
+    k, t = int(k), int(t)
+    cap = max(k, 1)
+    tt = max(t, 1)
+    sn = np.zeros(cap, dtype=np.int64)
+    sd = np.zeros(cap, dtype=np.int64)
+    ss = np.zeros(cap)
+    track = np.zeros((cap + 1, tt))
+    ns = C.c_int64()
+    ncm = C.c_int()
+    nrf = C.c_int()
+    p64 = C.POINTER(C.c_int64)
+    _lib.check(_lib.load().kt_miobi_break_node(
+        D.handle, k, t, int(refresh), 1 if shift == "first_order" else 0, float(tol), int(max_spmm),
+        int(seed) & 0xFFFFFFFFFFFFFFFF, sn.ctypes.data_as(p64), _dptr(ss), sd.ctypes.data_as(p64), _dptr(track),
+        C.byref(ns), C.byref(ncm), C.byref(nrf)))
+    D.n, D.nnz = D.info()
+    m = int(ns.value)
+    if ncm.value < t:
+        warnings.warn(f"miobi_break_node: eigs_topk converged nconv = {ncm.value} of the {t} eigenpairs in at least "
+                      "one run; the scores use the pairs as returned", RuntimeWarning, stacklevel=2)
+    lam1 = np.zeros(t) if D.nnz == 0 else eigs_topk(D, t, tol=tol, max_spmm=max_spmm, seed=seed, ctx=ctx)[0]
+    R0, R1 = _log_mean_exp(track[0]), _log_mean_exp(lam1)
+    info = {"scores": ss[:m].copy(), "degrees": sd[:m].copy(), "track": track[:m + 1].copy(),
+            "nconv_min": int(ncm.value), "refreshes": int(nrf.value), "R0": R0, "R1": R1,
+            "rob_score": (R0 - R1) * 100.0 / R0 if R0 != 0.0 else 0.0, "D": D}
+    return sn[:m] + 1, info
+
+
+def find_top_nodes_miobi(A, num, t=25, tol=0.0, max_spmm=0, seed=0, ctx: Optional[Context] = None):
+    """The top `num` nodes ranked by ascending MIOBI node score (the node
+    miobi_break_node would remove first comes first) from the leading t
+    eigenpairs of eigs_topk, column 0 by absolute value (MIOBIBreakNode.m:
+    176-204); 1-based, ties in node order.  Nodes without a neighbour score
+    +Inf and come last."""
+    from .core import eigs_topk
+    D = _dev(A, ctx)
+    n, _ = D.info()
+    num = int(np.floor(num))
+    if n < num:
+        raise IndexError("FIND_TOP_NODES:: there are not enough nodes in the graph")
+    lam, V = eigs_topk(D, t, tol=tol, max_spmm=max_spmm, seed=seed, ctx=ctx)
+    V = np.array(V, order="F")
+    V[:, 0] = np.abs(V[:, 0])
+    score = nodes_score_topk(D, lam, V, ctx=D.ctx)
+    return _stable_head(score, num) + 1
+
+
 def find_top_edges_miobi(A, num, t=25, tol=0.0, max_spmm=0, seed=0, ctx: Optional[Context] = None):
     """The top `num` existing edges ranked by ascending MIOBI score (the edge
     MIOBI would remove first comes first) from the leading t eigenpairs of

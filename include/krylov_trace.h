@@ -553,6 +553,46 @@ int kt_miobi_break_node(kt_matrix_t A, int k, int t, int refresh, int shift, dou
                         uint64_t seed, int64_t* sel, double* sel_score, int64_t* sel_deg,
                         double* lambda_track, int64_t* nsel, int* nconv_min, int* refreshes);
 
+/* Node removal scored exactly.  For every candidate node
+ * nodes[c] (0-based; duplicates are legal) Xm[c] ~= tr f(A_{-i}) - tr f(A),
+ * where A_{-i} is A with row and column i zeroed (the node stays as an isolated
+ * vertex, as kt_miobi_break_node leaves it).  Removing node i is a rank-2
+ * update whose block Krylov space is the single-vector space of e_i, so with
+ * T_j the Lanczos tridiagonal started at e_i
+ *   X_j = f(0) + sum f(eig(T_j[2:j, 2:j])) - sum f(eig(T_j)),
+ * and the stopping rule is trace_fun_update.m:104-124: stop at the first j > 2
+ * with |X_j - X_{j-2}| < tol (absolute, the tol of kt_trace_fun_update_pairs),
+ * or with lucky = 1 at a step whose beta_j < 1e-8.  The candidates are columns
+ * of explicit CGS2 sweeps 16 wide on up to four lanes, the rule applied on the
+ * device after every step; Xm comes from the host on the record cut at the
+ * column's depth, so a candidate's Xm, iter and lucky depend on (A, node, tol,
+ * it, fun) only -- not on what shares its sweep or its call -- bit for bit.
+ * tol <= 0: 1e-12.  it <= 0: min(100, n).  iter, lucky (nullable, ncand each):
+ * as kt_trace_fun_update's; a column that reaches `it` unstopped returns its
+ * last X with iter = it.  n <= 130 takes the dense host path (eig of A and of
+ * A_{-i}), iter = 0.
+ * KT_ERR_ARG before the device is touched for fun = KT_FUN_LOG (f(0) is not
+ * finite), it > 256, NULL arguments, a node index outside 0..n-1 or
+ * outstanding kt_slq_submit calls; KT_ERR_NOT_HERMITIAN for non-symmetric A. */
+int kt_trace_fun_update_nodes(kt_matrix_t A, int64_t ncand, const int64_t* nodes, double tol, int it,
+                              int fun, double* Xm, int* iter, int* lucky);
+
+/* The greedy loop over kt_trace_fun_update_nodes: up to k times, score every
+ * remaining candidate on the current A, take the smallest Xm (the first in
+ * the list on ties), zero that node's row and column in place (the edit
+ * kt_matrix_set_pairs makes), drop it from the list and add its Xm to *rob.
+ * Stops after k steps or when the list is empty.  Outputs: sel (0-based) and
+ * sel_xm (nullable), min(k, ncand) each; *rob (nullable) the summed Xm, an
+ * estimate of tr f(A_new) - tr f(A); *nsel the steps made.  Arguments and
+ * errors as kt_trace_fun_update_nodes', and k < 0. */
+int kt_krylov_break_node(kt_matrix_t A, int k, int64_t ncand, const int64_t* nodes, double tol, int it,
+                         int fun, int64_t* sel, double* sel_xm, double* rob, int64_t* nsel);
+
+/* The value kt_trace_fun_update_nodes forms at depth j: X_j above from the
+ * tridiagonal (alpha[0..j-1], off[0..j-2]) of a Lanczos run started at e_i, by
+ * the host QL.  1 <= j <= 256; fun any kt_fun but KT_FUN_LOG.  Host only. */
+int kt_host_node_update(int j, const double* alpha, const double* off, int fun, double* xm);
+
 /* Per-kernel timing (HIP events recorded on the library's stream around each
  * launch of the named kernel while enabled).  kernel: 0 = the probe-Lanczos
  * gather pass (k_spmm_lanczos in the y-form sweep, k_spmm_dot = K1 in the
@@ -579,7 +619,10 @@ int kt_miobi_break_node(kt_matrix_t A, int k, int t, int refresh, int shift, dou
  * k_miobi_make_pick),
  * 13 = kt_miobi_break_node's steps, one interval per step (k_miobi_node_score,
  * k_miobi_node_pick; a step queued past its window's end is a pair of no-op
- * launches), and kt_nodes_score_topk's scoring launch.
+ * launches), and kt_nodes_score_topk's scoring launch,
+ * 14 = kt_trace_fun_update_nodes' own launches: the stopping tests
+ * (k_node_check, one interval per sweep and depth) and the unit-vector starts
+ * (k_unit_start); its sweeps' passes report in 0 and 1.
  * Returns launch count and summed milliseconds. */
 int kt_profile_enable(kt_context_t ctx, int enable);
 int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* total_ms);
@@ -620,7 +663,10 @@ int kt_debug_delay(kt_context_t ctx, int lane, double microseconds);
  * microseconds of the last kt_miobi_make or kt_miobi_break_node call on this
  * context -- its eigensolver runs; its candidate ranking, mask construction
  * and uploads (kt_miobi_break_node: staging V, the eigenvalues and the window's
- * row lists); its edits of A. */
+ * row lists); its edits of A.  stats 13, 14, 15: of the last
+ * kt_trace_fun_update_nodes call on this context (kt_krylov_break_node: of its
+ * last greedy step) -- its sweeps, the sweep steps it queued (one SpMM pass
+ * over A each) and the depth of its deepest column. */
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value);
 
 /* Threads of the process-wide host pool (the per-column / per-candidate

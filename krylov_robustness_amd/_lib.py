@@ -120,6 +120,10 @@ SIGNATURES = [
     ("kt_nodes_score_topk", C.c_int, [_mat_p, C.c_int, _dp, _dp, _dp]),
     ("kt_miobi_break_node", C.c_int, [_mat_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_uint64,
                                       _i64p, _dp, _i64p, _dp, _i64p, _ip, _ip]),
+    ("kt_trace_fun_update_nodes", C.c_int, [_mat_p, C.c_int64, _i64p, C.c_double, C.c_int, C.c_int, _dp, _ip, _ip]),
+    ("kt_krylov_break_node", C.c_int, [_mat_p, C.c_int, C.c_int64, _i64p, C.c_double, C.c_int, C.c_int, _i64p, _dp,
+                                       _dp, _i64p]),
+    ("kt_host_node_update", C.c_int, [C.c_int, _dp, _dp, C.c_int, _dp]),
     ("kt_profile_enable", C.c_int, [_ctx_p, C.c_int]),
     ("kt_profile_read", C.c_int, [_ctx_p, C.c_int, _i64p, _dp]),
     ("kt_profile_reset", C.c_int, [_ctx_p]),

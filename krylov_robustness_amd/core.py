@@ -89,7 +89,9 @@ class Context:
         by slq_quadforms_auto, 9 thick restarts of eigs_topk calls, 10-12 host
         microseconds of the last miobi_make or miobi_break_node call
         (eigensolver runs; ranking, mask and uploads -- staging for
-        miobi_break_node; edits of A)."""
+        miobi_break_node; edits of A), 13-15 the last trace_fun_update_nodes
+        call's sweeps, queued sweep steps (one SpMM pass each) and deepest
+        column."""
         v = C.c_int64()
         _lib.check(_lib.load().kt_context_stat(self._h, int(which), C.byref(v)))
         return int(v.value)

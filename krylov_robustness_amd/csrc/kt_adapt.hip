@@ -4,6 +4,8 @@
 //
 // k_quad_check decides depths only; the values a call returns are formed on
 // the host from the record truncated at the depth chosen here.
+// k_node_check is the same for the node-removal columns of
+// lanczos_nodes_adaptive (§4.2h), k_unit_start their sweeps' start block.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -295,6 +297,160 @@ hipError_t launch_quad_check_wide(const double* trec, int mcap, int P, int j, in
     const int grid = (live + kWideCheckCols - 1) / kWideCheckCols;
     k_quad_check_wide<<<grid, 64, lds, st>>>(trec, mcap, P, j, live, nfe, n2, fun, rtol, state, running, guard,
                                              gmin, gsnap);
+    return hipGetLastError();
+}
+
+namespace {
+
+// ascending insertion sort of one lane's m values (stride G in LDS)
+__device__ __forceinline__ void dev_sort_strided(int m, int G, double* d) {
+    for (int i = 1; i < m; ++i) {
+        const double v = d[i * G];
+        int k = i - 1;
+        for (; k >= 0 && d[k * G] > v; --k) d[(k + 1) * G] = d[k * G];
+        d[(k + 1) * G] = v;
+    }
+}
+
+}  // namespace
+
+// The stopping test of a node-removal column at depth j (DESIGN.md §4.2h;
+// kt_slq.cpp lanczos_nodes_adaptive): k_quad_check's launch shape -- one
+// wavefront, lane t owns column c = g0 + t (t < G, c < live), LDS arrays
+// [k][lane] with stride G.  The column's sweep started at a unit vector e_i, so
+// with T_j the record's leading j x j tridiagonal
+//   X_j = trace_diff(sort({0} + eig(T_j[2:, 2:])), sort(eig(T_j)))
+// (two value-only QL runs) approximates tr f(A_{-i}) - tr f(A).  state:
+// kAdaptState doubles per column, zeroed before the sweep's first check,
+//   [0] X_j  [1] Xstop[0]  [2] Xstop[1]  [3] depth  [4] stopped  [5] theta_max_j
+//   [6] lucky  [7] the depth of the last check
+// fun = exp: the three X scaled by exp(-theta_max_j) (the stored two are
+// brought to each new depth's scale; theta_max grows with the depth), and tol
+// scaled the same way in the comparison, so nothing overflows below exp's own
+// range.  The rule is trace_fun_update.m:104-124: X_1 and X_2 are stored; for
+// j > 2 the column stops when |X_j - X_{j-2}| < tol, else the stored pair
+// moves up; a column that did not stop stops with lucky = 1 when the record's
+// beta_j (low[j-1]) < 1e-8.  The checks of a sweep run at consecutive depths
+// from 1; a stopped column is left as it is.  active[0]: as k_quad_check's.
+__global__ __launch_bounds__(64) void k_node_check(const double* __restrict__ trec, int mcap, int P, int j, int live,
+                                                   int g0, int G, int fun, double tol, double* __restrict__ state,
+                                                   int* __restrict__ active) {
+    extern __shared__ double sm[];
+    __shared__ int stopped_l[64];
+    const int t = threadIdx.x, c = g0 + t;
+    const bool mine = t < G && c < live;
+    int stopped = -1;
+    if (mine) {
+        double* st = state + (size_t)c * kAdaptState;
+        stopped = st[4] != 0.0;
+        if (!stopped) {
+            const double* al = trec + c;
+            const double* up = trec + (size_t)mcap * P + c;
+            const double* low = trec + (size_t)2 * mcap * P + c;
+            double* d2 = sm + t;
+            double* d1 = sm + (size_t)j * G + t;
+            double* e = sm + (size_t)2 * j * G + t;
+            double* z = sm + (size_t)3 * j * G + t;
+            for (int k = 0; k < j; ++k) d2[k * G] = al[(size_t)k * P];
+            for (int k = 0; k + 1 < j; ++k) e[k * G] = 0.5 * (low[(size_t)k * P] + up[(size_t)(k + 1) * P]);
+            dev_ql_rows<false>(j, G, d2, e, z, nullptr);
+            if (j > 1) {
+                for (int k = 0; k + 1 < j; ++k) d1[k * G] = al[(size_t)(k + 1) * P];
+                for (int k = 0; k + 2 < j; ++k)
+                    e[k * G] = 0.5 * (low[(size_t)(k + 1) * P] + up[(size_t)(k + 2) * P]);
+                dev_ql_rows<false>(j - 1, G, d1, e, z, nullptr);
+            }
+            d1[(j - 1) * G] = 0.0;  // the removed node stays as an isolated vertex: f(0)
+            dev_sort_strided(j, G, d1);
+            dev_sort_strided(j, G, d2);
+            const double tm = fmax(d1[(j - 1) * G], d2[(j - 1) * G]);
+            double x = 0.0;
+            if (fun == KT_FUN_EXP) {
+                for (int k = 0; k < j; ++k) x += exp(d1[k * G] - tm) * (1.0 - exp(d2[k * G] - d1[k * G]));
+            } else {
+                for (int k = 0; k < j; ++k) x += dev_fscalar(fun, d1[k * G]) - dev_fscalar(fun, d2[k * G]);
+            }
+            const bool ex = fun == KT_FUN_EXP;
+            const double r = (ex && j > 1) ? exp(st[5] - tm) : 1.0;  // the stored pair at this depth's scale
+            double x0 = st[1] * r, x1 = st[2] * r;
+            bool stop = false;
+            if (j == 1) {
+                x0 = x;
+            } else if (j == 2) {
+                x1 = x;
+            } else if (fabs(x - x0) < (ex ? tol * exp(-tm) : tol)) {
+                stop = true;
+            } else {
+                x0 = x1;
+                x1 = x;
+            }
+            const bool lucky = low[(size_t)(j - 1) * P] < 1e-8;
+            if (!stop && lucky) stop = true;
+            st[0] = x;
+            st[1] = x0;
+            st[2] = x1;
+            st[5] = ex ? tm : 0.0;
+            st[7] = (double)j;
+            if (stop) {
+                st[3] = (double)j;
+                st[4] = 1.0;
+                st[6] = lucky ? 1.0 : 0.0;
+                stopped = 1;
+            }
+        }
+    }
+    stopped_l[t] = stopped;
+    __syncthreads();
+    if (t == 0) {
+        int run = 0;
+        for (int k = 0; k < live; ++k) {
+            const bool here = k >= g0 && k < g0 + G;  // another group's columns: an earlier launch wrote them
+            run += here ? (stopped_l[k - g0] == 0) : (state[(size_t)k * kAdaptState + 4] == 0.0);
+        }
+        active[0] = run;
+    }
+}
+
+// P <= 32 columns, 1 <= j <= mcap <= 256.  The four LDS arrays of depth j take
+// 32 j G bytes: every live column in one launch while they fit 64 KB together
+// with the kernel's static words (P = 16 up to depth 127), else column groups
+// of 8 lanes per launch, and of 4 at the depths where 8 lanes' arrays alone
+// are 64 KB (j = 256); each group's count is taken over all live columns.
+hipError_t launch_node_check(const double* trec, int mcap, int P, int j, int live, int fun, double tol, double* state,
+                             int* active, hipStream_t st) {
+    if (P < 1 || P > 32 || live < 1 || live > P || j < 1 || j > mcap || mcap > 256) return hipErrorInvalidValue;
+    const size_t room = (size_t)65536 - 512;
+    int G = P;
+    if ((size_t)32 * j * G > room) G = 8;
+    if ((size_t)32 * j * G > room) G = 4;
+    for (int g0 = 0; g0 < live; g0 += G) {
+        k_node_check<<<1, 64, sizeof(double) * 4 * j * G, st>>>(trec, mcap, P, j, live, g0, G, fun, tol, state, active);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// The start of a node-removal sweep: column c < nc of the zeroed n x P block X
+// gets 1 at row pos[c] (the candidate's row in the sweep's row order; duplicate
+// rows are legal, each in its own column), and the sweep's start scale and
+// squared norm (sc, k2s: P each) are 1 for those columns, 0 for the padding.
+__global__ __launch_bounds__(64) void k_unit_start(int n, int P, int nc, const int* __restrict__ pos,
+                                                   double* __restrict__ X, double* __restrict__ sc,
+                                                   double* __restrict__ k2s) {
+    const int c = threadIdx.x;
+    if (c >= P) return;
+    const int r = c < nc ? pos[c] : -1;
+    const bool ok = r >= 0 && r < n;
+    if (ok) X[(size_t)r * P + c] = 1.0;
+    sc[c] = ok ? 1.0 : 0.0;
+    k2s[c] = ok ? 1.0 : 0.0;
+}
+
+hipError_t launch_unit_start(int n, int P, int nc, const int* pos, double* X, double* sc, double* k2s,
+                             hipStream_t st) {
+    if (n < 1 || P < 1 || P > 64 || nc < 0 || nc > P) return hipErrorInvalidValue;
+    k_unit_start<<<1, 64, 0, st>>>(n, P, nc, pos, X, sc, k2s);
     return hipGetLastError();
 }
 

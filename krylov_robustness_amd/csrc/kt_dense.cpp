@@ -217,6 +217,41 @@ DepthTest tridiag_depth_test(int j, const double* alpha, const double* off, int 
     return t;
 }
 
+// The node-removal update at depth j from the Lanczos tridiagonal started at
+// e_i: removing node i takes the first row and column out of
+// T_j, the node staying as an isolated vertex, so
+//   X_j = f(0) + sum f(eig(T_j[2:j, 2:j])) - sum f(eig(T_j)),
+// summed as trace_diff sums it (kt_krylov.cpp; trace_fun_update.m:85-89: the
+// two spectra sorted and paired, fun = exp in the form that does not cancel).
+// scale (nullable): sum |f(eig(T_j))|, what a test holds the value's error to;
+// tmax (nullable): the largest of the 2 j values, the device test's exp scale.
+double node_update_value(int j, const double* alpha, const double* off, int fun, double* scale, double* tmax) {
+    if (j <= 0) return 0.0;
+    std::vector<double> d2(alpha, alpha + j), d1(j, 0.0), e(j, 0.0), z(j);
+    for (int i = 0; i + 1 < j; ++i) e[i] = off[i];
+    ql_first_row(j, d2.data(), e.data(), z.data());
+    if (j > 1) {
+        for (int i = 0; i + 1 < j; ++i) d1[i] = alpha[i + 1];
+        std::fill(e.begin(), e.end(), 0.0);
+        for (int i = 0; i + 2 < j; ++i) e[i] = off[i + 1];
+        ql_first_row(j - 1, d1.data(), e.data(), z.data());
+    }
+    d1[j - 1] = 0.0;
+    std::sort(d1.begin(), d1.end());
+    std::sort(d2.begin(), d2.end());
+    double x = 0.0, s = 0.0;
+    for (int i = 0; i < j; ++i) {
+        if (fun == KT_FUN_EXP)
+            x += std::exp(d1[i]) * (1.0 - std::exp(d2[i] - d1[i]));
+        else
+            x += fscalar(fun, d1[i]) - fscalar(fun, d2[i]);
+        s += std::fabs(fscalar(fun, d2[i]));
+    }
+    if (scale) *scale = s;
+    if (tmax) *tmax = std::max(d1[j - 1], d2[j - 1]);
+    return x;
+}
+
 }  // namespace kt
 
 // ---------------------------------------------------------------------------
@@ -579,6 +614,16 @@ extern "C" int kt_host_quad_converged(int j, const double* alpha, const double* 
         kt::tridiag_depth_test(j, alpha, off, fun, want_fe1 != 0, rtol > 0.0 ? rtol : kt::kAdaptRtol);
     *converged = t.converged ? 1 : 0;
     *q = t.q;
+    return KT_OK;
+}
+
+extern "C" int kt_host_node_update(int j, const double* alpha, const double* off, int fun, double* xm) {
+    if (j < 1 || j > kt::kAdaptMaxCap || !alpha || (j > 1 && !off) || !xm || fun < KT_FUN_EXP || fun > KT_FUN_SQRT ||
+        fun == KT_FUN_LOG) {
+        kt::set_error("kt_host_node_update: bad argument (1 <= j <= 256, non-NULL arrays and output, fun not log)");
+        return KT_ERR_ARG;
+    }
+    *xm = kt::node_update_value(j, alpha, off, fun);
     return KT_OK;
 }
 

@@ -145,11 +145,13 @@ struct ProfSlot {
 // kt_pairs_score_topk scoring launch.  PROF_MIOBI_MAKE: one interval per
 // kt_miobi_make step (k_miobi_make_score, k_miobi_make_pick).  PROF_MIOBI_NODE:
 // one interval per kt_miobi_break_node step (k_miobi_node_score,
-// k_miobi_node_pick) and per kt_nodes_score_topk scoring launch
+// k_miobi_node_pick) and per kt_nodes_score_topk scoring launch.  PROF_NODES:
+// kt_trace_fun_update_nodes' own launches, one interval per stopping test
+// (k_node_check, every column group of a depth) and per start (k_unit_start)
 enum {
     PROF_SPMM = 0, PROF_UPDATE = 1, PROF_START = 2, PROF_YBLOCK = 3, PROF_EXPMV = 4, PROF_FIRST = 5,
     PROF_CHECK = 6, PROF_DIAG = 7, PROF_DIAG_START = 8, PROF_ENTRIES = 9, PROF_EIGS = 10, PROF_MIOBI = 11,
-    PROF_MIOBI_MAKE = 12, PROF_MIOBI_NODE = 13, PROF_NSLOTS = 14
+    PROF_MIOBI_MAKE = 12, PROF_MIOBI_NODE = 13, PROF_NODES = 14, PROF_NSLOTS = 15
 };
 
 // Buffers of one probe-sweep lane (kt_slq.cpp); two lanes let two sweeps
@@ -236,6 +238,7 @@ struct Workspace {
     // still-active columns), the pinned words the host polls and their events
     DevBuf adapt_state[4];
     PinnedBuf pin_adapt;
+    DevBuf node_pos;  // lanczos_nodes_adaptive: the candidates' rows in the sweeps' order
     // kt_slq_trace_auto: per lane the check's device block (state, guard
     // snapshot, running words), the ring of polled copies and their events
     DevBuf auto_state[4];
@@ -271,6 +274,9 @@ struct kt_context_s {
     // its eigensolver runs; its candidate ranking, mask construction and uploads
     // (break_node: staging V, e and the window's row lists); its edits of A
     int64_t make_eig_us = 0, make_rank_us = 0, make_edit_us = 0;
+    // the last kt_trace_fun_update_nodes call (or greedy step of kt_krylov_break_node):
+    // its sweeps, the sweep steps it queued (one SpMM pass each) and its deepest column
+    int64_t nodes_sweeps = 0, nodes_steps = 0, nodes_max_depth = 0;
     int ky_flags = 8;   // y-form pass flags (8 = nontemporal store of y_{j+1}, +0.3 %)
     bool yform = true;  // KT_SLQ_YFORM=0: the hot path runs the explicit K1/K2 sweep
     void* blas = nullptr;  // rocblas_handle, created on first block-Krylov use
@@ -418,6 +424,11 @@ struct DepthTest {
     double r1 = INFINITY, r2 = INFINITY, r3 = 0.0;  // the test's three ratios (each against rtol)
 };
 DepthTest tridiag_depth_test(int j, const double* alpha, const double* off, int fun, int want_fe1, double rtol);
+// The node-removal trace update at depth j from the tridiagonal of the Lanczos
+// run started at e_i (kt_dense.cpp); scale (nullable):
+// sum |f(eig(T_j))|; tmax (nullable): the largest eigenvalue either sum takes.
+double node_update_value(int j, const double* alpha, const double* off, int fun, double* scale = nullptr,
+                         double* tmax = nullptr);
 bool chol_upper(double* G, int n);
 void tri_upper_inv(const double* R, int n, double* X);
 void sym_eig_host(int n, const double* A, double* w, double* V);

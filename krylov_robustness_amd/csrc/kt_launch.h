@@ -154,6 +154,19 @@ hipError_t launch_quad_check_wide(const double* trec, int mcap, int P, int j, in
                                   const double* guard = nullptr, double gmin = 0.0, double* gsnap = nullptr);
 hipError_t launch_weighted_sum_tab(int n, int m, int nc, const SlotTab& tab, int spc, const double* W, double* Y,
                                    int ldy, hipStream_t st);
+// The node-removal columns (kt_slq.cpp lanczos_nodes_adaptive; DESIGN.md
+// §4.2h).  launch_node_check: launch_quad_check's shape and state block for
+// the lag-2 rule of trace_fun_update.m:104-124 on X_j = f(0) + sum f(eig(T_j[2:,
+// 2:])) - sum f(eig(T_j)), tol absolute; state per column: [0] X_j [1] [2] the
+// stored pair [3] depth [4] stopped [5] theta_max_j [6] lucky [7] last depth
+// (fun = exp: the X scaled by exp(-theta_max_j)).  launch_unit_start: column
+// c < nc of the zeroed n x P block X gets 1 at row pos[c] (device array, rows
+// in the sweep's order; out of range: the column stays zero), sc / k2s (P
+// each) the start scale and squared norm.
+hipError_t launch_node_check(const double* trec, int mcap, int P, int j, int live, int fun, double tol, double* state,
+                             int* active, hipStream_t st);
+hipError_t launch_unit_start(int n, int P, int nc, const int* pos, double* X, double* sc, double* k2s,
+                             hipStream_t st);
 hipError_t launch_fill(double* x, int count, double v, hipStream_t st);
 hipError_t launch_delay(double microseconds, hipStream_t st);
 // sweep start scales from device column norms (kt_slq.cpp; mode 0 explicit: sc,

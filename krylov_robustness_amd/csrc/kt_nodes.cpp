@@ -1,0 +1,146 @@
+// kt_nodes.cpp -- node removal scored exactly:
+// kt_trace_fun_update_nodes, Xm ~= tr f(A_{-i}) - tr f(A) for a list of nodes
+// (A_{-i}: row and column i zeroed, the node left as an isolated vertex), and
+// kt_krylov_break_node, the greedy loop over it.
+//
+// Removing node i is a rank-2 update whose block Krylov space is the
+// single-vector space K_{j+1}(A, e_i), so the candidates are columns of the
+// sweep engine (kt_slq.cpp lanczos_nodes_adaptive; the stopping test is
+// kt_adapt.hip k_node_check).  n <= 130 takes the dense host path, as
+// trace_fun_update.m:37-51 does.
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "kt_krylov.h"
+#include "kt_slq.h"
+
+namespace kt {
+
+namespace {
+
+// dense path: eig(A) once, eig(A_{-i}) per candidate, on the host
+void nodes_dense(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, int fun, double* Xm, int* iter, int* lucky) {
+    const int n = (int)A->n;
+    std::vector<double> D((size_t)n * n, 0.0), w2(n), w1(n);
+    for (int r = 0; r < n; ++r)
+        for (int64_t k = A->h_rowptr[r]; k < A->h_rowptr[r + 1]; ++k) D[r + (size_t)A->h_col[k] * n] = A->h_val[k];
+    sym_eig_host(n, D.data(), w2.data(), nullptr);
+    std::sort(w2.begin(), w2.end());
+    for (int64_t c = 0; c < ncand; ++c) {
+        std::vector<double> Di = D;
+        const int64_t i = nodes[c];
+        for (int r = 0; r < n; ++r) Di[r + (size_t)i * n] = Di[i + (size_t)r * n] = 0.0;
+        sym_eig_host(n, Di.data(), w1.data(), nullptr);
+        std::sort(w1.begin(), w1.end());
+        Xm[c] = trace_diff(w1, w2, fun);
+        if (iter) iter[c] = 0;
+        if (lucky) lucky[c] = 0;
+    }
+}
+
+// what both entries check before the device is touched: first what needs no
+// matrix, then (node_checks) the rest; returns `it` resolved
+void scalar_checks(int64_t ncand, int it, int fun, const char* who) {
+    const std::string w(who);
+    if (ncand < 0) fail(KT_ERR_ARG, w + ": negative candidate count");
+    if (fun < KT_FUN_EXP || fun > KT_FUN_SQRT) fail(KT_ERR_ARG, w + ": unknown fun");
+    if (fun == KT_FUN_LOG) fail(KT_ERR_ARG, w + ": fun = log is not supported (f(0) of the isolated node is not finite)");
+    if (it > kAdaptMaxCap) fail(KT_ERR_ARG, w + ": it must be at most 256");
+}
+
+int node_checks(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, double& tol, int it, const char* who) {
+    const std::string w(who);
+    if (A->n > INT32_MAX) fail(KT_ERR_ARG, w + ": n must fit 32-bit indices");
+    for (int64_t c = 0; c < ncand; ++c)
+        if (nodes[c] < 0 || nodes[c] >= A->n) fail(KT_ERR_ARG, w + ": node index out of range");
+    if (A->ctx->ws.slq_submitted != A->ctx->ws.slq_collected)
+        fail(KT_ERR_ARG, w + ": kt_slq_submit calls are outstanding on this context");
+    require_symmetric(A, "TRACE_FUN_UPDATE_NODES:: symmetric A required");
+    if (!(tol > 0.0)) tol = 1e-12;
+    if (it <= 0) it = (int)std::min<int64_t>(100, A->n);  // trace_fun_update.m:25-27
+    return it;
+}
+
+void nodes_update(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, double tol, int it, int fun, double* Xm,
+                  int* iter, int* lucky) {
+    if (ncand == 0) return;
+    if (A->n <= 130) {
+        nodes_dense(A, ncand, nodes, fun, Xm, iter, lucky);
+        return;
+    }
+    KT_HIP(hipSetDevice(A->ctx->device));
+    prof_recycle(A->ctx);
+    lanczos_nodes_adaptive(A, ncand, nodes, tol, it, fun, Xm, iter, lucky);
+}
+
+}  // namespace
+
+}  // namespace kt
+
+using namespace kt;
+
+#define KT_NODES_GUARD_END                             \
+    catch (const Status& s) {                          \
+        set_error(s.msg);                              \
+        return s.code;                                 \
+    }                                                  \
+    catch (const std::bad_alloc&) {                    \
+        set_error("host allocation failed");           \
+        return KT_ERR_ALLOC;                           \
+    }                                                  \
+    return KT_OK;
+
+extern "C" int kt_trace_fun_update_nodes(kt_matrix_t A, int64_t ncand, const int64_t* nodes, double tol, int it,
+                                         int fun, double* Xm, int* iter, int* lucky) {
+    try {
+        scalar_checks(ncand, it, fun, "kt_trace_fun_update_nodes");
+        if (!A || (ncand > 0 && (!nodes || !Xm))) fail(KT_ERR_ARG, "kt_trace_fun_update_nodes: NULL argument");
+        it = node_checks(A, ncand, nodes, tol, it, "kt_trace_fun_update_nodes");
+        nodes_update(A, ncand, nodes, tol, it, fun, Xm, iter, lucky);
+    }
+    KT_NODES_GUARD_END
+}
+
+extern "C" int kt_krylov_break_node(kt_matrix_t A, int k, int64_t ncand, const int64_t* nodes, double tol, int it,
+                                    int fun, int64_t* sel, double* sel_xm, double* rob, int64_t* nsel) {
+    try {
+        scalar_checks(ncand, it, fun, "kt_krylov_break_node");
+        if (!A || !nsel || (ncand > 0 && !nodes) || (k > 0 && ncand > 0 && !sel))
+            fail(KT_ERR_ARG, "kt_krylov_break_node: NULL argument");
+        if (k < 0) fail(KT_ERR_ARG, "kt_krylov_break_node: k must not be negative");
+        it = node_checks(A, ncand, nodes, tol, it, "kt_krylov_break_node");
+        *nsel = 0;
+        if (rob) *rob = 0.0;
+        std::vector<int64_t> cand(nodes, nodes + ncand), ei, ej;
+        std::vector<double> xm;
+        double total = 0.0;
+        for (int s = 0; s < k && !cand.empty(); ++s) {
+            xm.assign(cand.size(), 0.0);
+            nodes_update(A, (int64_t)cand.size(), cand.data(), tol, it, fun, xm.data(), nullptr, nullptr);
+            size_t best = 0;  // the smallest Xm, the first on ties
+            for (size_t c = 1; c < cand.size(); ++c)
+                if (xm[c] < xm[best]) best = c;
+            const int64_t r = cand[best];
+            // the node's row and column out of A: one host-ordered edit per step
+            ei.clear();
+            ej.clear();
+            for (int64_t q = A->h_rowptr[r]; q < A->h_rowptr[r + 1]; ++q) {
+                ei.push_back(r);
+                ej.push_back(A->h_col[q]);
+            }
+            if (!ei.empty()) {
+                KT_HIP(hipSetDevice(A->ctx->device));
+                set_pairs(A, (int64_t)ei.size(), ei.data(), ej.data(), 0.0);
+            }
+            sel[s] = r;
+            if (sel_xm) sel_xm[s] = xm[best];
+            total += xm[best];
+            if (rob) *rob = total;
+            *nsel = s + 1;
+            cand.erase(cand.begin() + (std::ptrdiff_t)best);
+        }
+    }
+    KT_NODES_GUARD_END
+}

@@ -609,11 +609,12 @@ int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* tot
 
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value) {
     KT_GUARD_BEGIN
-    if (!ctx || !value || stat < 0 || stat > 12) fail(KT_ERR_ARG, "bad stat query");
-    const int64_t v[13] = {ctx->yform_redone, ctx->fu_dense, ctx->fu_last_cols, ctx->expmv_calls,
+    if (!ctx || !value || stat < 0 || stat > 15) fail(KT_ERR_ARG, "bad stat query");
+    const int64_t v[16] = {ctx->yform_redone, ctx->fu_dense, ctx->fu_last_cols, ctx->expmv_calls,
                           ctx->expmv_terms, ctx->adapt_max_depth, ctx->adapt_capped, ctx->int0_sweeps,
                           ctx->auto_passes, ctx->eigs_restarts, ctx->make_eig_us,
-                          ctx->make_rank_us, ctx->make_edit_us};
+                          ctx->make_rank_us, ctx->make_edit_us, ctx->nodes_sweeps, ctx->nodes_steps,
+                          ctx->nodes_max_depth};
     *value = v[stat];
     KT_GUARD_END
 }

@@ -102,7 +102,10 @@ ExplicitSweep::ExplicitSweep(kt_matrix_s* A_, const DevCSR& M_, int P_, int m_, 
 
 void ExplicitSweep::start() {
     hipStream_t st = L.st;
-    if (!x) {
+    if (unit_pos) {
+        KT_HIP(hipMemsetAsync(ucur, 0, L.blk_bytes, st));
+        KT_HIP(launch_unit_start(n, P, ncols, unit_pos, ucur, sc, k2s, st));
+    } else if (!x) {
         KT_HIP(launch_rademacher(P, n, seed, probe_base, M.perm, ucur, st));
         KT_HIP(launch_fill(sc, P, 1.0 / std::sqrt((double)n), st));
         KT_HIP(launch_fill(k2s, P, (double)n, st));  // ||z||^2 = n
@@ -128,6 +131,8 @@ void ExplicitSweep::use_basis_chunks(std::vector<DevMat>* chunks_, int spc_) {
     chunks = chunks_;
     spc = spc_;
 }
+
+void ExplicitSweep::use_unit_start(const int* pos_dev) { unit_pos = pos_dev; }
 
 // basis slot j (nullptr: the sweep keeps no basis)
 double* ExplicitSweep::slot(int j) {
@@ -824,6 +829,134 @@ int lanczos_columns_adaptive(kt_matrix_s* A, const double* X, int ldx, int ncols
     ctx->adapt_max_depth = std::max<int64_t>(ctx->adapt_max_depth, dmax);
     ctx->adapt_capped += ncap;
     return ncap;
+}
+
+// The node-removal columns: lanczos_columns_adaptive's
+// driver -- sweeps kAdaptP wide, one per lane at a time, the check of depth
+// j + 1 queued behind step j, the count of running columns polled every
+// kAdaptPoll steps one poll behind -- for sweeps that start at unit vectors
+// (k_unit_start, rows through the hub copy's permutation) and stop by
+// k_node_check's lag-2 rule from depth 1 on.  The explicit CGS2 sweep: a hub's
+// unit vector sits close to the dominant eigenvector, where the y-form's
+// cancellation guard would trip.  The device decides depths; Xm comes from the
+// host QL on the record cut at the column's depth, so a candidate's values
+// depend on (A, node, tol, it, fun) alone.
+void lanczos_nodes_adaptive(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, double tol, int it, int fun,
+                            double* Xm, int* iter, int* lucky) {
+    kt_context_s* ctx = A->ctx;
+    const int64_t n = A->n;
+    if (ncand < 1) return;
+    if (it < 1 || it > kAdaptMaxCap) fail(KT_ERR_ARG, "the Lanczos depth cap must be in [1, 256]");
+    if (ncand > INT32_MAX - kAdaptP || n > INT32_MAX) fail(KT_ERR_ARG, "n and the candidate count must fit 32 bits");
+    const int m = it, P = kAdaptP, ncols = (int)ncand;
+    const DevCSR& M = hub_csr(A);
+    const bool relabelled = M.perm != nullptr;
+    std::vector<int> hpos((size_t)ncols);
+    for (int c = 0; c < ncols; ++c) {
+        if (nodes[c] < 0 || nodes[c] >= n) fail(KT_ERR_ARG, "node index out of range");
+        hpos[c] = relabelled ? A->old2new[nodes[c]] : (int)nodes[c];
+    }
+    DevBuf& dposb = ctx->ws.node_pos;
+    dposb.ensure(sizeof(int) * (size_t)ncols);
+    const int* dpos = dposb.as<int>();
+    KT_HIP(hipMemcpyAsync(dposb.ptr, hpos.data(), sizeof(int) * (size_t)ncols, hipMemcpyHostToDevice, ctx->stream));
+    KT_HIP(hipStreamSynchronize(ctx->stream));  // the lanes read it; hpos may go
+    const int nsw = (ncols + P - 1) / P;
+    const size_t rec = (size_t)3 * m * P, stw = (size_t)P * kAdaptState;
+    PinnedBuf& hr = ctx->ws.pin_colrec;  // per sweep its record and state block
+    hr.ensure(sizeof(double) * (rec + stw) * nsw);
+    PinnedBuf& pw = ctx->ws.pin_adapt;  // the polled words: [lane][2]
+    pw.ensure(sizeof(int) * 8);
+    volatile int* polled = pw.as<int>();
+    const int lanes = std::min(4, nsw);
+    for (int l = 0; l < lanes; ++l) {
+        (void)lane_stream(ctx, l);
+        for (auto& e : ctx->ws.adapt_ev[l])
+            if (!e) KT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        ctx->ws.adapt_state[l].ensure(sizeof(double) * (stw + 1));
+    }
+    std::vector<int> rows(nsw, 0);  // record rows written per sweep
+    int64_t steps_queued = 0;
+    for (int s0 = 0; s0 < nsw; s0 += lanes) {
+        const int g = std::min(lanes, nsw - s0);
+        std::vector<std::unique_ptr<ExplicitSweep>> ex;
+        std::vector<char> done(g, 0);
+        for (int l = 0; l < g; ++l) {
+            const int i = s0 + l, c0 = i * P, nc = std::min(P, ncols - c0);
+            double* R = hr.as<double>() + (rec + stw) * i;
+            ex.emplace_back(new ExplicitSweep(A, M, P, m, 0, 0, nullptr, 0, nc, nullptr, R, nullptr, nullptr, l, 0));
+            ex.back()->use_unit_start(dpos + c0);
+            KT_HIP(hipMemsetAsync(ctx->ws.adapt_state[l].ptr, 0, sizeof(double) * (stw + 1), ex.back()->stream()));
+            polled[2 * l] = polled[2 * l + 1] = 1;
+        }
+        for (auto& e : ex) {
+            prof_begin(ctx, PROF_NODES, e->stream(), P);
+            e->start();
+            prof_end(ctx, PROF_NODES, e->stream());
+        }
+        int npoll = 0;
+        for (int j = 0; j < m; ++j) {
+            bool any = false;
+            for (int l = 0; l < g; ++l) {
+                if (done[l]) continue;
+                any = true;
+                const int i = s0 + l, c0 = i * P, nc = std::min(P, ncols - c0);
+                ExplicitSweep& e = *ex[l];
+                e.step(j);
+                ++steps_queued;
+                rows[i] = j + 1;
+                double* dst = ctx->ws.adapt_state[l].as<double>();
+                int* dact = reinterpret_cast<int*>(dst + stw);
+                prof_begin(ctx, PROF_NODES, e.stream(), P);
+                KT_HIP(launch_node_check(e.device_record(), m, P, j + 1, nc, fun, tol, dst, dact, e.stream()));
+                prof_end(ctx, PROF_NODES, e.stream());
+                if ((j + 1) % kAdaptPoll == 0) {
+                    int* word = const_cast<int*>(polled) + 2 * l + (npoll & 1);
+                    KT_HIP(hipMemcpyAsync(word, dact, sizeof(int), hipMemcpyDeviceToHost, e.stream()));
+                    KT_HIP(hipEventRecord(ctx->ws.adapt_ev[l][npoll & 1], e.stream()));
+                }
+            }
+            if (!any) break;
+            if ((j + 1) % kAdaptPoll == 0) {
+                // the poll before this one: its event has kAdaptPoll steps queued behind it
+                if (npoll > 0)
+                    for (int l = 0; l < g; ++l) {
+                        if (done[l]) continue;
+                        KT_HIP(hipEventSynchronize(ctx->ws.adapt_ev[l][(npoll - 1) & 1]));
+                        if (polled[2 * l + ((npoll - 1) & 1)] == 0) done[l] = 1;
+                    }
+                ++npoll;
+            }
+        }
+        for (int l = 0; l < g; ++l) {
+            const int i = s0 + l;
+            ex[l]->finish(rows[i]);
+            KT_HIP(hipMemcpyAsync(hr.as<double>() + (rec + stw) * i + rec, ctx->ws.adapt_state[l].ptr,
+                                  sizeof(double) * stw, hipMemcpyDeviceToHost, ex[l]->stream()));
+        }
+        // the lanes' buffers and state blocks are reused by the next group
+        KT_HIP(hipStreamSynchronize(ctx->stream));
+        for (int l = 1; l < g; ++l) KT_HIP(hipStreamSynchronize(ctx->aux_stream[l - 1]));
+    }
+    std::vector<int> dep(ncols, 0);
+    HostPool::get().run(ncols, [&](int t) {
+        const int i = t / P, c = t % P;
+        const double* R = hr.as<double>() + (rec + stw) * i;
+        const double* st = R + rec + (size_t)c * kAdaptState;
+        // a column the device did not stop ran every row the sweep wrote: iter = it
+        const int d = std::max(1, std::min(st[4] != 0.0 ? (int)st[3] : rows[i], rows[i]));
+        std::vector<double> al(d), off(d);
+        for (int k = 0; k < d; ++k) al[k] = R[(size_t)k * P + c];
+        for (int k = 0; k + 1 < d; ++k)
+            off[k] = 0.5 * (R[(size_t)(2 * m + k) * P + c] + R[(size_t)(1 * m + k + 1) * P + c]);
+        Xm[t] = node_update_value(d, al.data(), off.data(), fun);
+        dep[t] = d;
+        if (iter) iter[t] = d;
+        if (lucky) lucky[t] = R[(size_t)(2 * m + d - 1) * P + c] < 1e-8 ? 1 : 0;
+    }, 4);
+    ctx->nodes_sweeps = nsw;
+    ctx->nodes_steps = steps_queued;
+    ctx->nodes_max_depth = *std::max_element(dep.begin(), dep.end());
 }
 
 static bool pow2_le128(int b) { return b >= 1 && b <= 128 && (b & (b - 1)) == 0; }

@@ -66,6 +66,11 @@ class ExplicitSweep : public Sweep {
     // instead of one m-slot block: pass basis = nullptr and call this before
     // start().
     void use_basis_chunks(std::vector<DevMat>* chunks, int spc);
+    // The unit-vector start (lanczos_nodes_adaptive): a sweep constructed with
+    // x = nullptr and ncols columns starts column c at e_{pos[c]}, pos a device
+    // array of rows in M's order, instead of the RNG's probes (kt_adapt.hip
+    // k_unit_start).  Call before start().
+    void use_unit_start(const int* pos_dev);
     void finish(int rows);
     const double* device_record() const { return trec; }
     hipStream_t stream() const { return L.st; }
@@ -74,6 +79,7 @@ class ExplicitSweep : public Sweep {
     double* slot(int j);
     std::vector<DevMat>* chunks = nullptr;
     int spc = 0;
+    const int* unit_pos = nullptr;
     kt_matrix_s* A;
     const DevCSR& M;
     int P, m;
@@ -228,6 +234,21 @@ void lanczos_columns_split(kt_matrix_s* A, const double* X, int ldx, int ncols, 
 // context's stats (kt_context_stat 5, 6) follow.
 int lanczos_columns_adaptive(kt_matrix_s* A, const double* X, int ldx, int ncols, int ny, int m_max, double rtol,
                              int fun, double* quad, double* Y, int ldy, int* depth = nullptr);
+
+// Node removal: for every candidate node i_c (0-based,
+// duplicates legal) Xm[c] ~= tr f(A_{-i}) - tr f(A), A_{-i} = A with row and
+// column i zeroed, from the single-vector Lanczos run started at e_i: with T_j
+// its tridiagonal, X_j = f(0) + sum f(eig(T_j[2:, 2:])) - sum f(eig(T_j)).
+// Candidates are columns of explicit CGS2 sweeps, always 16 wide, on up to
+// four lanes; after every step the device applies trace_fun_update.m's lag-2
+// rule (kt_adapt.hip k_node_check; tol absolute, lucky at beta_j < 1e-8) and a
+// sweep is queued until its columns have all stopped or reached `it` (1..256).
+// Xm is formed on the host from the record cut at the column's depth, so it
+// depends on (A, i, tol, it, fun) only.  iter / lucky (nullable): the depth and
+// whether its beta broke down; a column that reaches `it` unstopped returns
+// its last X with iter = it.  The context's stats 13-15 follow.
+void lanczos_nodes_adaptive(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, double tol, int it, int fun,
+                            double* Xm, int* iter, int* lucky);
 
 // y-form sweep seeded by a device block (see kt_slq.cpp)
 void lanczos_sweep_y_block(kt_matrix_s* A, const DevCSR& M, int P, int m, const double* x, int ldx, int ncols,

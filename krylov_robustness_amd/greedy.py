@@ -604,6 +604,75 @@ def miobi_break_node(A, k, t=25, refresh=50, shift="reference", tol=0.0, max_spm
     return sn[:m] + 1, info
 
 
+def _node_args(who, A, nodes, it, fun):
+    """What the node entries reject before a device is touched; nodes 0-based."""
+    code = _fun_code(fun)
+    if code == _lib.FUN_CODES["log"]:
+        raise _lib.KrylovError(_lib.KT_ERR_ARG, f"{who}: fun = log is not supported (f(0) of the isolated node "
+                                                "is not finite)")
+    if it is not None and int(it) > 256:
+        raise _lib.KrylovError(_lib.KT_ERR_ARG, f"{who}: it must be at most 256")
+    nodes = np.asarray(nodes, dtype=np.int64).ravel() - 1
+    n = A.n if isinstance(A, DeviceMatrix) else A.shape[0]
+    if nodes.size and (nodes.min() < 0 or nodes.max() >= n):
+        raise _lib.KrylovError(_lib.KT_ERR_ARG, f"{who}: node index out of range (1-based, 1..{n})")
+    return code, nodes
+
+
+def trace_fun_update_nodes(A, nodes, tol=1e-12, it=None, fun="exp", ctx: Optional[Context] = None):
+    """Xm[c] ~= trace(f(A_{-i})) - trace(f(A)) for every node i of `nodes`
+    (1-based, as miobi_break_node's; duplicates are legal), A_{-i} being A with
+    row and column i zeroed -- the node stays as an isolated vertex.  From the
+    single-vector Lanczos run started at e_i (kt_trace_fun_update_nodes;
+    DESIGN.md §4.2h) with trace_fun_update's stopping rule: tol is absolute
+    and means what it means to trace_fun_update_pairs.  A candidate's values do
+    not depend on the other candidates of the call.  fun "log" is rejected.
+    The rule's first test compares X_3 with X_1: a tol above both stops the
+    column at depth 3 whatever its limit is, which happens to hubs of large
+    graphs at tol ~ 1e-6 exp(normest(A)); check iter.
+    Returns (Xm, iter, lucky) arrays."""
+    code, nd = _node_args("trace_fun_update_nodes", A, nodes, it, fun)
+    D = _dev(A, ctx)
+    q = nd.size
+    nd, pn = _i64(nd)
+    xm = np.zeros(max(q, 1))
+    itr = np.zeros(max(q, 1), dtype=np.int32)
+    lk = np.zeros(max(q, 1), dtype=np.int32)
+    _lib.check(_lib.load().kt_trace_fun_update_nodes(
+        D.handle, q, pn, float(tol), int(it or 0), code, _dptr(xm),
+        itr.ctypes.data_as(C.POINTER(C.c_int)), lk.ctypes.data_as(C.POINTER(C.c_int))))
+    return xm[:q], itr[:q], lk[:q]
+
+
+def krylov_break_node(A, k, nodes, tol=1e-12, it=None, fun="exp", ctx: Optional[Context] = None):
+    """Greedy node removal scored by trace_fun_update_nodes: up to k times, score
+    every remaining candidate of `nodes` (1-based; find_top_nodes_miobi or a
+    degree ranking can feed it) on the current matrix, remove the one with the
+    smallest Xm (the first on ties) -- its row and column are zeroed -- and drop
+    it from the list (kt_krylov_break_node).  A DeviceMatrix is edited in place.
+
+    Returns (nodes, rob, D, info): the removed nodes (1-based, fewer than k when
+    the list ran out), rob = the summed Xm ~= trace(f(A_new)) - trace(f(A)), the
+    edited DeviceMatrix, and info: "xm", the Xm of each removed node when it was
+    removed."""
+    code, nd = _node_args("krylov_break_node", A, nodes, it, fun)
+    D = _dev(A, ctx)
+    k = int(k)
+    q = nd.size
+    nd, pn = _i64(nd)
+    cap = max(min(k, q), 1)
+    sn = np.zeros(cap, dtype=np.int64)
+    sx = np.zeros(cap)
+    rob = C.c_double()
+    ns = C.c_int64()
+    _lib.check(_lib.load().kt_krylov_break_node(
+        D.handle, k, q, pn, float(tol), int(it or 0), code, sn.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(sx),
+        C.byref(rob), C.byref(ns)))
+    D.n, D.nnz = D.info()
+    m = int(ns.value)
+    return sn[:m] + 1, float(rob.value), D, {"xm": sx[:m].copy()}
+
+
 def find_top_nodes_miobi(A, num, t=25, tol=0.0, max_spmm=0, seed=0, ctx: Optional[Context] = None):
     """The top `num` nodes ranked by ascending MIOBI node score (the node
     miobi_break_node would remove first comes first) from the leading t

@@ -660,10 +660,12 @@ int kt_debug_delay(kt_context_t ctx, int lane, double microseconds);
  * kt_slq_trace_auto calls (those queued past a sweep's last stop, which
  * return at once, included), since context creation.  stat 9: thick restarts
  * of kt_eigs_topk calls, since context creation.  stats 10, 11, 12: host
- * microseconds of the last kt_miobi_make or kt_miobi_break_node call on this
- * context -- its eigensolver runs; its candidate ranking, mask construction
- * and uploads (kt_miobi_break_node: staging V, the eigenvalues and the window's
- * row lists); its edits of A.  stats 13, 14, 15: of the last
+ * microseconds of the last kt_miobi_break, kt_miobi_make or
+ * kt_miobi_break_node call on this context that got as far as its first
+ * eigensolver run -- its eigensolver runs; its candidate ranking, mask
+ * construction and uploads (kt_miobi_break: staging V and the eigenvalues;
+ * kt_miobi_break_node: those and the window's row lists); its edits of A.
+ * stats 13, 14, 15: of the last
  * kt_trace_fun_update_nodes call on this context (kt_krylov_break_node: of its
  * last greedy step) -- its sweeps, the sweep steps it queued (one SpMM pass
  * over A each) and the depth of its deepest column. */

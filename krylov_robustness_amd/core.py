@@ -87,9 +87,9 @@ class Context:
         Lanczos Afun used, 6 its columns that reached the depth cap, 7 y-form
         sweeps that carried y_0 as int16 row sums, 8 y-form step passes queued
         by slq_quadforms_auto, 9 thick restarts of eigs_topk calls, 10-12 host
-        microseconds of the last miobi_make or miobi_break_node call
-        (eigensolver runs; ranking, mask and uploads -- staging for
-        miobi_break_node; edits of A), 13-15 the last trace_fun_update_nodes
+        microseconds of the last miobi_break, miobi_make or miobi_break_node
+        call (eigensolver runs; ranking, mask and uploads -- staging for
+        miobi_break and miobi_break_node; edits of A), 13-15 the last trace_fun_update_nodes
         call's sweeps, queued sweep steps (one SpMM pass each) and deepest
         column."""
         v = C.c_int64()

@@ -1,17 +1,35 @@
-// kt_miobi_host.h -- the host-only parts of kt_miobi_make's driver
-// (kt_miobi.cpp): the candidate ranking, the adjacency
+// kt_miobi_host.h -- the host-only parts of the MIOBI drivers (kt_miobi.cpp):
+// of their shared window loop, the edge window length and the step-count
+// check; of kt_miobi_make's: the candidate ranking, the adjacency
 // bitmask of the candidate block and the bookkeeping of the candidate count m;
 // and of kt_miobi_break_node's (§4.2g): the argument scan, the window length,
 // the removed-entry count replayed, the long-row list and the row / column
 // removal.  Plain C++ with no device call, so that a stand-alone host program
 // can run them under a sanitizer (tests/native/miobi_make_check/host_san.cpp,
-// tests/native/miobi_node_check/host_san.cpp).
+// tests/native/miobi_node_check/host_san.cpp,
+// tests/native/miobi_window_check/host_san.cpp).
 #pragma once
 #include <algorithm>
 #include <cstdint>
 #include <vector>
 
 namespace kt {
+
+// ---- the window loop all three drivers share -------------------------------
+
+// the steps to queue for one window of the edge drivers (kt_miobi_break,
+// kt_miobi_make): up to the next multiple of `refresh` steps, where the
+// eigenpairs are recomputed (MIOBIBreakEdge2.m:255, MIOBIMakeEdge.m:326);
+// refresh <= 0: all that remain
+inline int miobi_edge_window(int remaining, int done, int refresh) {
+    return refresh > 0 ? std::min(remaining, refresh - done % refresh) : remaining;
+}
+
+// whether the device's step count after a window of w queued steps can be
+// right: it started at `done` and every step adds one or, past a stop, nothing
+inline bool miobi_step_in_window(int now, int done, int w) { return now >= done && now <= done + w; }
+
+// ---- make (kt_miobi_make, MIOBIMakeEdge.m) ---------------------------------
 
 // max(sum(A, 2)) of a unit-weight matrix: the longest row (MIOBIMakeEdge.m:60-61)
 inline int miobi_max_degree(int64_t n, const int64_t* rowptr) {

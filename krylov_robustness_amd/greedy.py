@@ -423,6 +423,45 @@ def _log_mean_exp(lam):
     return float(np.log(np.sum(np.exp(lam - lam[0]))) + lam[0] - np.log(lam.size))
 
 
+def _miobi_run(name, A, k, t, lead, tol, max_spmm, seed, ctx, outputs, gain=False, empty_R1=True):
+    """What miobi_break, miobi_make and miobi_break_node share: the call of the
+    library's kt_<name>(A, k, t, *lead, tol, max_spmm, seed, <outputs>, nsel,
+    nconv_min, refreshes) and what is made of its results.  outputs: the
+    entry's output arguments in its order -- an int64 column of k rows each but
+    "score" (float64), "m" (int32), "track" ((k + 1) x t) and "V" (n x t,
+    column-major); None passes NULL.  gain: rob_score is (R1 - R0) 100 / R0, an
+    addition's, and not (R0 - R1) 100 / R0.  empty_R1: R1 of a matrix left
+    without an entry is that of t zero eigenvalues, with no eigs_topk run.
+    Returns (the integer columns cut to nsel rows, info)."""
+    from .core import eigs_topk
+    D = _dev(A, ctx)
+    n, _ = D.info()
+    k, t = int(k), int(t)
+    cap, tt = max(k, 1), max(t, 1)
+    kinds = {"score": (cap, np.float64, "C"), "m": (cap, np.int32, "C"), "track": ((cap + 1, tt), np.float64, "C"),
+             "V": ((max(n, 1), tt), np.float64, "F")}
+    out = {o: np.zeros(*kinds.get(o, (cap, np.int64, "C"))) for o in outputs if o}
+    ns, ncm, nrf = C.c_int64(), C.c_int(), C.c_int()
+    _lib.check(getattr(_lib.load(), "kt_" + name)(
+        D.handle, k, t, *lead, float(tol), int(max_spmm), int(seed) & 0xFFFFFFFFFFFFFFFF,
+        *(out[o].ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(out[o].dtype))) if o else None for o in outputs),
+        C.byref(ns), C.byref(ncm), C.byref(nrf)))
+    D.n, D.nnz = D.info()
+    m = int(ns.value)
+    if ncm.value < t:
+        warnings.warn(f"{name}: eigs_topk converged nconv = {ncm.value} of the {t} eigenpairs in at least one "
+                      "run; the scores use the pairs as returned", RuntimeWarning, stacklevel=3)
+    lam1 = (np.zeros(t) if empty_R1 and D.nnz == 0
+            else eigs_topk(D, t, tol=tol, max_spmm=max_spmm, seed=seed, ctx=ctx)[0])
+    R0, R1 = _log_mean_exp(out["track"][0]), _log_mean_exp(lam1)
+    info = {"scores": out["score"][:m].copy(), "track": out["track"][:m + 1].copy(), "nconv_min": int(ncm.value),
+            "refreshes": int(nrf.value), "R0": R0, "R1": R1,
+            "rob_score": ((R1 - R0) if gain else (R0 - R1)) * 100.0 / R0 if R0 != 0.0 else 0.0, "D": D}
+    if "V" in out:
+        info["V"] = np.asarray(out["V"][:n])
+    return {o: a[:m].copy() for o, a in out.items() if o not in ("score", "track", "V")}, info
+
+
 def miobi_break(A, k, t=25, refresh=50, mode="reference", gap_rel=0.0, tol=0.0, max_spmm=0, seed=0,
                 return_V=False, ctx: Optional[Context] = None):
     """MIOBI's top-t edge removal on the device (MIOBIBreakEdge2.m and
@@ -442,41 +481,11 @@ def miobi_break(A, k, t=25, refresh=50, mode="reference", gap_rel=0.0, tol=0.0, 
     after, "rob_score" = (R0 - R1) 100 / R0 (:40-42, :266-268), "D" the edited
     DeviceMatrix, and "V" (n x t, the vectors after the last step) with
     return_V."""
-    from .core import eigs_topk
     if mode not in ("reference", "paper"):
         raise _lib.KrylovError(_lib.KT_ERR_ARG, "miobi_break: mode must be 'reference' or 'paper'")
-    D = _dev(A, ctx)
-    n, _ = D.info()
-    k, t = int(k), int(t)
-    cap = max(k, 1)
-    tt = max(t, 1)
-    si = np.zeros(cap, dtype=np.int64)
-    sj = np.zeros(cap, dtype=np.int64)
-    ss = np.zeros(cap)
-    track = np.zeros((cap + 1, tt))
-    Vf = np.zeros((max(n, 1), tt), order="F") if return_V else None
-    ns = C.c_int64()
-    ncm = C.c_int()
-    nrf = C.c_int()
-    p64 = C.POINTER(C.c_int64)
-    _lib.check(_lib.load().kt_miobi_break(
-        D.handle, k, t, int(refresh), 1 if mode == "paper" else 0, float(gap_rel), float(tol), int(max_spmm),
-        int(seed) & 0xFFFFFFFFFFFFFFFF, si.ctypes.data_as(p64), sj.ctypes.data_as(p64), _dptr(ss), _dptr(track),
-        _dptr(Vf) if return_V else None, C.byref(ns), C.byref(ncm), C.byref(nrf)))
-    D.n, D.nnz = D.info()
-    m = int(ns.value)
-    if ncm.value < t:
-        warnings.warn(f"miobi_break: eigs_topk converged nconv = {ncm.value} of the {t} eigenpairs in at least one "
-                      "run; the scores use the pairs as returned", RuntimeWarning, stacklevel=2)
-    edges = np.stack([si[:m] + 1, sj[:m] + 1], axis=1)
-    lam1 = np.zeros(t) if D.nnz == 0 else eigs_topk(D, t, tol=tol, max_spmm=max_spmm, seed=seed, ctx=ctx)[0]
-    R0, R1 = _log_mean_exp(track[0]), _log_mean_exp(lam1)
-    info = {"scores": ss[:m].copy(), "track": track[:m + 1].copy(), "nconv_min": int(ncm.value),
-            "refreshes": int(nrf.value), "R0": R0, "R1": R1,
-            "rob_score": (R0 - R1) * 100.0 / R0 if R0 != 0.0 else 0.0, "D": D}
-    if return_V:
-        info["V"] = np.asarray(Vf[:n])
-    return edges, info
+    cols, info = _miobi_run("miobi_break", A, k, t, (int(refresh), 1 if mode == "paper" else 0, float(gap_rel)),
+                            tol, max_spmm, seed, ctx, ("i", "j", "score", "track", "V" if return_V else None))
+    return np.stack([cols["i"] + 1, cols["j"] + 1], axis=1), info
 
 
 def miobi_make(A, k, t=25, refresh=50, tol=0.0, max_spmm=0, seed=0, ctx: Optional[Context] = None):
@@ -499,36 +508,10 @@ def miobi_make(A, k, t=25, refresh=50, tol=0.0, max_spmm=0, seed=0, ctx: Optiona
     "R0" / "R1" = log(mean(exp(lam))) of eigs_topk(., t) before and after,
     "rob_score" = (R1 - R0) 100 / R0 (:44, :186-188), and "D" the edited
     DeviceMatrix."""
-    from .core import eigs_topk
-    D = _dev(A, ctx)
-    k, t = int(k), int(t)
-    cap = max(k, 1)
-    tt = max(t, 1)
-    si = np.zeros(cap, dtype=np.int64)
-    sj = np.zeros(cap, dtype=np.int64)
-    ss = np.zeros(cap)
-    cm = np.zeros(cap, dtype=np.int32)
-    track = np.zeros((cap + 1, tt))
-    ns = C.c_int64()
-    ncm = C.c_int()
-    nrf = C.c_int()
-    p64 = C.POINTER(C.c_int64)
-    _lib.check(_lib.load().kt_miobi_make(
-        D.handle, k, t, int(refresh), float(tol), int(max_spmm), int(seed) & 0xFFFFFFFFFFFFFFFF,
-        si.ctypes.data_as(p64), sj.ctypes.data_as(p64), _dptr(ss), _dptr(track),
-        cm.ctypes.data_as(C.POINTER(C.c_int)), C.byref(ns), C.byref(ncm), C.byref(nrf)))
-    D.n, D.nnz = D.info()
-    m = int(ns.value)
-    if ncm.value < t:
-        warnings.warn(f"miobi_make: eigs_topk converged nconv = {ncm.value} of the {t} eigenpairs in at least one "
-                      "run; the scores use the pairs as returned", RuntimeWarning, stacklevel=2)
-    edges = np.stack([si[:m] + 1, sj[:m] + 1], axis=1)
-    lam1 = eigs_topk(D, t, tol=tol, max_spmm=max_spmm, seed=seed, ctx=ctx)[0]
-    R0, R1 = _log_mean_exp(track[0]), _log_mean_exp(lam1)
-    info = {"scores": ss[:m].copy(), "track": track[:m + 1].copy(), "m": cm[:m].astype(np.int64),
-            "nconv_min": int(ncm.value), "refreshes": int(nrf.value), "R0": R0, "R1": R1,
-            "rob_score": (R1 - R0) * 100.0 / R0 if R0 != 0.0 else 0.0, "D": D}
-    return edges, info
+    cols, info = _miobi_run("miobi_make", A, k, t, (int(refresh),), tol, max_spmm, seed, ctx,
+                            ("i", "j", "score", "track", "m"), gain=True, empty_R1=False)
+    info = {"scores": info.pop("scores"), "track": info.pop("track"), "m": cols["m"].astype(np.int64), **info}
+    return np.stack([cols["i"] + 1, cols["j"] + 1], axis=1), info
 
 
 def nodes_score_topk(A, lam, V, ctx: Optional[Context] = None):
@@ -572,36 +555,12 @@ def miobi_break_node(A, k, t=25, refresh=50, shift="reference", tol=0.0, max_spm
     "nconv_min", "refreshes", "R0" / "R1" = log(mean(exp(lam))) of
     eigs_topk(., t) before and after, "rob_score" = (R0 - R1) 100 / R0
     (:299-301), and "D" the edited DeviceMatrix."""
-    from .core import eigs_topk
     if shift not in ("reference", "first_order"):
         raise _lib.KrylovError(_lib.KT_ERR_ARG, "miobi_break_node: shift must be 'reference' or 'first_order'")
-    D = _dev(A, ctx)
-    k, t = int(k), int(t)
-    cap = max(k, 1)
-    tt = max(t, 1)
-    sn = np.zeros(cap, dtype=np.int64)
-    sd = np.zeros(cap, dtype=np.int64)
-    ss = np.zeros(cap)
-    track = np.zeros((cap + 1, tt))
-    ns = C.c_int64()
-    ncm = C.c_int()
-    nrf = C.c_int()
-    p64 = C.POINTER(C.c_int64)
-    _lib.check(_lib.load().kt_miobi_break_node(
-        D.handle, k, t, int(refresh), 1 if shift == "first_order" else 0, float(tol), int(max_spmm),
-        int(seed) & 0xFFFFFFFFFFFFFFFF, sn.ctypes.data_as(p64), _dptr(ss), sd.ctypes.data_as(p64), _dptr(track),
-        C.byref(ns), C.byref(ncm), C.byref(nrf)))
-    D.n, D.nnz = D.info()
-    m = int(ns.value)
-    if ncm.value < t:
-        warnings.warn(f"miobi_break_node: eigs_topk converged nconv = {ncm.value} of the {t} eigenpairs in at least "
-                      "one run; the scores use the pairs as returned", RuntimeWarning, stacklevel=2)
-    lam1 = np.zeros(t) if D.nnz == 0 else eigs_topk(D, t, tol=tol, max_spmm=max_spmm, seed=seed, ctx=ctx)[0]
-    R0, R1 = _log_mean_exp(track[0]), _log_mean_exp(lam1)
-    info = {"scores": ss[:m].copy(), "degrees": sd[:m].copy(), "track": track[:m + 1].copy(),
-            "nconv_min": int(ncm.value), "refreshes": int(nrf.value), "R0": R0, "R1": R1,
-            "rob_score": (R0 - R1) * 100.0 / R0 if R0 != 0.0 else 0.0, "D": D}
-    return sn[:m] + 1, info
+    cols, info = _miobi_run("miobi_break_node", A, k, t, (int(refresh), 1 if shift == "first_order" else 0),
+                            tol, max_spmm, seed, ctx, ("node", "score", "degree", "track"))
+    info = {"scores": info.pop("scores"), "degrees": cols["degree"], **info}
+    return cols["node"] + 1, info
 
 
 def _node_args(who, A, nodes, it, fun):

@@ -63,6 +63,9 @@ hipError_t launch_pair_fused(int C, int n, int64_t nnz, const CsrView& A, bool u
 // owning threads -- so the list order is part of the kernel's arithmetic
 constexpr int kRegLongCap = 256;
 bool pair_reg_applies(int n, int64_t nnz, int it, int n_long, bool unit);
+// the k_pair_reg<rows, csr> instance and `spec` value that shape takes (what
+// pair_reg_applies decides on; rows = 0 when it does not apply)
+bool pair_reg_form(int n, int64_t nnz, int it, int n_long, bool unit, int* rows, int* csr, int* spec);
 hipError_t launch_pair_reg_dyn(int C, int n, int64_t nnz_max, const CsrView& A, bool unit, const int* ii,
                                const int* jj, const double* B, int it, int fun, double tol, double* state,
                                const int* dyn, hipStream_t st);

@@ -2362,6 +2362,14 @@ bool pair_reg_applies(int n, int64_t nnz, int it, int n_long, bool unit) {
     return pair_reg_plan(n, nnz, it, n_long, unit).applies;
 }
 
+bool pair_reg_form(int n, int64_t nnz, int it, int n_long, bool unit, int* rows, int* csr, int* spec) {
+    const PairRegPlan p = pair_reg_plan(n, nnz, it, n_long, unit);
+    *rows = p.applies ? p.rows : 0;
+    *csr = p.csr;
+    *spec = p.spec;
+    return p.applies;
+}
+
 // the k_pair_reg<R, CSR> instance of a plan; dyn: see launch_pair_reg_dyn
 static hipError_t launch_pair_reg(const PairRegPlan& p, int C, int n, int64_t nnz, const FusedCSR& M, const int* ii,
                                   const int* jj, const double* B, int it, int fun, double tol, double* state,

@@ -443,7 +443,9 @@ __global__ __launch_bounds__(kDiagBlock) void k_entries_accumulate(int64_t npair
 //         - (sum_c (QH)[i, c] Q[j, c] + (QH)[j, c] Q[i, c]) / 2,  (i, j) = tab[e].zw
 // (Q, G n x ld row-major in original row numbering; H k x k column-major).
 // Each column's two products are rounded and added symmetrically, so (i, j)
-// and (j, i) give the same bits.
+// and (j, i) give the same bits.  The column loop is compiled without
+// contraction: __dmul_rn / __dadd_rn are plain operators here, and an fma of
+// one product onto the other rounds (i, j) and (j, i) differently.
 __global__ __launch_bounds__(256) void k_entries_e0(int64_t npairs, const int4* __restrict__ tab, int k,
                                                     const double* __restrict__ Q, const double* __restrict__ G,
                                                     int ld, const double* __restrict__ H,
@@ -460,13 +462,14 @@ __global__ __launch_bounds__(256) void k_entries_e0(int64_t npairs, const int4* 
         const double* gj = G + (int64_t)pe.w * ld;
         double a = 0.0, b2 = 0.0;
         for (int c = 0; c < k; ++c) {
-            a += __dadd_rn(__dmul_rn(qi[c], gj[c]), __dmul_rn(gi[c], qj[c]));
+#pragma clang fp contract(off)
+            a += qi[c] * gj[c] + gi[c] * qj[c];
             double hi = 0.0, hj = 0.0;
             for (int b = 0; b < k; ++b) {
                 hi = fma(qi[b], sH[b + c * k], hi);
                 hj = fma(qj[b], sH[b + c * k], hj);
             }
-            b2 += __dadd_rn(__dmul_rn(hi, qj[c]), __dmul_rn(hj, qi[c]));
+            b2 += hi * qj[c] + hj * qi[c];
         }
         e0[e] = a - 0.5 * b2;
     }

@@ -593,6 +593,45 @@ int kt_krylov_break_node(kt_matrix_t A, int k, int64_t ncand, const int64_t* nod
  * the host QL.  1 <= j <= 256; fun any kt_fun but KT_FUN_LOG.  Host only. */
 int kt_host_node_update(int j, const double* alpha, const double* off, int fun, double* xm);
 
+/* Proved bounds on subgraph centrality.  For every candidate
+ * node nodes[c] (0-based; duplicates are legal) lo[c] <= exp(A)_ii <= hi[c] by
+ * Golub-Meurant quadrature on the Lanczos run started at e_i: with T_j its
+ * tridiagonal, the Gauss rule sum z_k^2 exp(theta_k) over the eigenpairs of
+ * T_j is a lower bound, and the Gauss-Radau rule -- the same sum over T_j
+ * bordered by beta_j with last diagonal entry lam_hi + beta_j^2 / d_j, d the
+ * pivots of T_j - lam_hi I -- an upper bound when lam_hi >= lambda_max(A); both
+ * tighten monotonically with j.  The bounds hold for f = exp only (every
+ * derivative positive), so the entry takes no kt_fun.  The candidates are
+ * columns of kt_trace_fun_update_nodes' sweeps (explicit CGS2, 16 wide, up to
+ * four lanes) with the bracket evaluated on the device after every step; a
+ * column stops at the first depth j with
+ *   flag 1: beta_j < 1e-8 -- the Gauss rule is exact, hi = lo;
+ *   flag 2: a Ritz value of T_j above lam_hi or a pivot d_k >= 0 -- lam_hi is
+ *           proved to be below lambda_max(A); lo still holds, hi is NaN;
+ *   flag 0: hi - lo <= rtol lo;
+ *   flag 3: j = it, the last bracket, still a valid one (also a column the
+ *           device stopped on a gap that the returned values miss by rounding).
+ * lo, hi and flag come from the host on the record cut at the column's depth
+ * (kt_host_gauss_radau), so a candidate's lo, hi, iter and flag depend on (A,
+ * node, lam_hi, rtol, it) only -- not on what shares its sweep or its call --
+ * bit for bit.  Both sums are formed scaled by exp(-lam_hi) and multiplied by
+ * exp(lam_hi) once.  rtol <= 0: 1e-10.  it <= 0: min(100, n).  iter, flag
+ * (nullable, ncand each).  n <= 130 takes the dense host path (lo = hi = the
+ * diagonal of exp(A) from one eigendecomposition), iter = 0, flag = 0.
+ * KT_ERR_ARG before the device is touched for NULL arguments, a node index
+ * outside 0..n-1, it > 256, a lam_hi that is not finite or above 700, or
+ * outstanding kt_slq_submit calls; KT_ERR_NOT_HERMITIAN for non-symmetric A. */
+int kt_diag_fun_bracket(kt_matrix_t A, int64_t ncand, const int64_t* nodes, double lam_hi, double rtol, int it,
+                        double* lo, double* hi, int* iter, int* flag);
+
+/* The bracket kt_diag_fun_bracket forms at depth j from the tridiagonal
+ * (alpha[0..j-1], off[0..j-2]) of a Lanczos run started at e_i, its next
+ * off-diagonal beta_j and the Radau node mu, by the host QL: *lo and *hi (times
+ * exp(mu)), *flag 0 a bracket, 1 beta_j < 1e-8 (hi = lo), 2 mu proved below
+ * lambda_max (hi = NaN).  1 <= j <= 256, mu finite and <= 700.  Host only. */
+int kt_host_gauss_radau(int j, const double* alpha, const double* off, double beta_j, double mu, double* lo,
+                        double* hi, int* flag);
+
 /* Per-kernel timing (HIP events recorded on the library's stream around each
  * launch of the named kernel while enabled).  kernel: 0 = the probe-Lanczos
  * gather pass (k_spmm_lanczos in the y-form sweep, k_spmm_dot = K1 in the
@@ -622,7 +661,8 @@ int kt_host_node_update(int j, const double* alpha, const double* off, int fun, 
  * launches), and kt_nodes_score_topk's scoring launch,
  * 14 = kt_trace_fun_update_nodes' own launches: the stopping tests
  * (k_node_check, one interval per sweep and depth) and the unit-vector starts
- * (k_unit_start); its sweeps' passes report in 0 and 1.
+ * (k_unit_start); its sweeps' passes report in 0 and 1.  kt_diag_fun_bracket's
+ * (k_bracket_check, k_unit_start) report here too.
  * Returns launch count and summed milliseconds. */
 int kt_profile_enable(kt_context_t ctx, int enable);
 int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* total_ms);
@@ -667,8 +707,8 @@ int kt_debug_delay(kt_context_t ctx, int lane, double microseconds);
  * kt_miobi_break_node: those and the window's row lists); its edits of A.
  * stats 13, 14, 15: of the last
  * kt_trace_fun_update_nodes call on this context (kt_krylov_break_node: of its
- * last greedy step) -- its sweeps, the sweep steps it queued (one SpMM pass
- * over A each) and the depth of its deepest column. */
+ * last greedy step) or kt_diag_fun_bracket call -- its sweeps, the sweep steps
+ * it queued (one SpMM pass over A each) and the depth of its deepest column. */
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value);
 
 /* Threads of the process-wide host pool (the per-column / per-candidate

@@ -5,7 +5,8 @@
 // k_quad_check decides depths only; the values a call returns are formed on
 // the host from the record truncated at the depth chosen here.
 // k_node_check is the same for the node-removal columns of
-// lanczos_nodes_adaptive (§4.2h), k_unit_start their sweeps' start block.
+// lanczos_nodes_adaptive (§4.2h), k_unit_start their sweeps' start block, and
+// k_bracket_check the test of lanczos_nodes_bracket's columns (§4.2i).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -425,6 +426,124 @@ hipError_t launch_node_check(const double* trec, int mcap, int P, int j, int liv
     if ((size_t)32 * j * G > room) G = 4;
     for (int g0 = 0; g0 < live; g0 += G) {
         k_node_check<<<1, 64, sizeof(double) * 4 * j * G, st>>>(trec, mcap, P, j, live, g0, G, fun, tol, state, active);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// The stopping test of a bracket column at depth j (kt_slq.cpp
+// lanczos_nodes_bracket): k_node_check's launch shape and state block -- one
+// wavefront, lane t owns column c = g0 + t (t < G, c < live), LDS arrays
+// [k][lane] with stride G.  With T_j the record's leading j x j tridiagonal of
+// the sweep started at e_i, beta_j = low[j-1] and mu >= lambda_max(A):
+//   L_j = sum z_k^2 exp(theta_k - mu) over the eigenpairs of T_j (Gauss),
+//   U_j = the same sum over T_j bordered by beta_j with last diagonal entry
+//         mu + beta_j^2 / d_j (Gauss-Radau, a node at mu),
+// d the pivots of T_j - mu I, run in registers.  Two dev_ql_rows<false> runs on
+// three LDS arrays of depth j + 1 (d, e, z).  state: kAdaptState doubles per
+// column, zeroed before the sweep's first check,
+//   [0] L_j  [1] U_j (both scaled by exp(-mu))  [3] depth  [4] stopped
+//   [6] flag  [7] the depth of the last check
+// The column stops with flag 1 when beta_j < 1e-8 (U := L), else with flag 2
+// when a pivot is not negative or a Ritz value lies above mu (U := NaN), else
+// with flag 0 when U_j - L_j <= rtol L_j, else with flag 3 at j = mcap.  A
+// stopped column is left as it is.  active[0]: as k_quad_check's.
+__global__ __launch_bounds__(64) void k_bracket_check(const double* __restrict__ trec, int mcap, int P, int j,
+                                                      int live, int g0, int G, double mu, double rtol,
+                                                      double* __restrict__ state, int* __restrict__ active) {
+    extern __shared__ double sm[];
+    __shared__ int stopped_l[64];
+    const int t = threadIdx.x, c = g0 + t;
+    const bool mine = t < G && c < live;
+    int stopped = -1;
+    if (mine) {
+        double* st = state + (size_t)c * kAdaptState;
+        stopped = st[4] != 0.0;
+        if (!stopped) {
+            const double* al = trec + c;
+            const double* up = trec + (size_t)mcap * P + c;
+            const double* low = trec + (size_t)2 * mcap * P + c;
+            double* d = sm + t;
+            double* e = sm + (size_t)(j + 1) * G + t;
+            double* z = sm + (size_t)2 * (j + 1) * G + t;
+            double dk = al[0] - mu;
+            bool bad = !(dk < 0.0);
+            d[0] = al[0];
+            for (int k = 1; k < j; ++k) {
+                const double b = 0.5 * (low[(size_t)(k - 1) * P] + up[(size_t)k * P]);
+                e[(k - 1) * G] = b;
+                d[k * G] = al[(size_t)k * P];
+                dk = al[(size_t)k * P] - mu - b * b / dk;
+                bad = bad || !(dk < 0.0);
+            }
+            dev_ql_rows<false>(j, G, d, e, z, nullptr);
+            double tm = d[0], lo = 0.0;
+            for (int k = 0; k < j; ++k) {
+                tm = fmax(tm, d[k * G]);
+                lo += z[k * G] * z[k * G] * exp(d[k * G] - mu);
+            }
+            const double bj = low[(size_t)(j - 1) * P];
+            double hi = lo;
+            int flag = -1;
+            if (bj < 1e-8) {
+                flag = 1;
+            } else if (bad || tm > mu) {
+                flag = 2;
+                hi = NAN;
+            } else {
+                d[0] = al[0];
+                for (int k = 1; k < j; ++k) {
+                    e[(k - 1) * G] = 0.5 * (low[(size_t)(k - 1) * P] + up[(size_t)k * P]);
+                    d[k * G] = al[(size_t)k * P];
+                }
+                e[(j - 1) * G] = bj;
+                d[j * G] = mu + bj * bj / dk;
+                dev_ql_rows<false>(j + 1, G, d, e, z, nullptr);
+                hi = 0.0;
+                for (int k = 0; k <= j; ++k) hi += z[k * G] * z[k * G] * exp(d[k * G] - mu);
+                if (hi - lo <= rtol * lo)
+                    flag = 0;
+                else if (j == mcap)
+                    flag = 3;
+            }
+            st[0] = lo;
+            st[1] = hi;
+            st[7] = (double)j;
+            if (flag >= 0) {
+                st[3] = (double)j;
+                st[4] = 1.0;
+                st[6] = (double)flag;
+                stopped = 1;
+            }
+        }
+    }
+    stopped_l[t] = stopped;
+    __syncthreads();
+    if (t == 0) {
+        int run = 0;
+        for (int k = 0; k < live; ++k) {
+            const bool here = k >= g0 && k < g0 + G;  // another group's columns: an earlier launch wrote them
+            run += here ? (stopped_l[k - g0] == 0) : (state[(size_t)k * kAdaptState + 4] == 0.0);
+        }
+        active[0] = run;
+    }
+}
+
+// P <= 32 columns, 1 <= j <= mcap <= 256.  The three LDS arrays of depth j + 1
+// take 24 (j + 1) G bytes: every live column in one launch while they fit 64 KB
+// together with the kernel's static words (P = 16 up to depth 168), else column
+// groups of 8 lanes per launch (48.2 KB at depth 256); each group's count is
+// taken over all live columns.
+hipError_t launch_bracket_check(const double* trec, int mcap, int P, int j, int live, double mu, double rtol,
+                                double* state, int* active, hipStream_t st) {
+    if (P < 1 || P > 32 || live < 1 || live > P || j < 1 || j > mcap || mcap > 256) return hipErrorInvalidValue;
+    const size_t room = (size_t)65536 - 512;
+    const size_t per_lane = sizeof(double) * 3 * (size_t)(j + 1);
+    const int G = (per_lane * P <= room) ? P : 8;
+    if (per_lane * G > room) return hipErrorInvalidValue;
+    for (int g0 = 0; g0 < live; g0 += G) {
+        k_bracket_check<<<1, 64, per_lane * G, st>>>(trec, mcap, P, j, live, g0, G, mu, rtol, state, active);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

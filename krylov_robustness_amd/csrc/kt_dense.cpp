@@ -252,6 +252,67 @@ double node_update_value(int j, const double* alpha, const double* off, int fun,
     return x;
 }
 
+// The Gauss / Gauss-Radau bracket of exp(A)_ii at depth j from the Lanczos
+// tridiagonal started at e_i (Golub & Meurant, Matrices,
+// Moments and Quadrature, 1994): with (theta, z) the eigenvalues of T_j and the
+// first row of its eigenvector matrix, lo = sum z_k^2 exp(theta_k - mu) is a
+// lower bound of exp(A)_ii exp(-mu); T_j bordered by beta_j with last diagonal
+// entry mu + beta_j^2 / d_j (d the pivots of T_j - mu I: d_1 = alpha_1 - mu,
+// d_k = alpha_k - mu - beta_{k-1}^2 / d_{k-1}) has an eigenvalue at mu, and the
+// same sum over its j + 1 pairs, hi, is an upper bound when mu >= lambda_max(A).
+// Returns 0 (a bracket), 1 (beta_j < 1e-8: the Gauss rule is exact, hi = lo) or
+// 2 (a pivot that is not negative, or a Ritz value above mu: mu is below
+// lambda_max(A); lo holds, hi is NaN).  scales (nullable, 2): sum exp(theta_k -
+// mu) over the eigenvalues of T_j and of the bordered matrix (0 when it was not
+// formed), what a test holds the sums' errors to: the QL gives the weights
+// z_k^2 to an absolute accuracy.
+int gauss_radau_sums(int j, const double* alpha, const double* off, double beta_j, double mu, double* lo,
+                     double* hi, double* scales) {
+    std::vector<double> d(alpha, alpha + j), e(j + 1, 0.0), z(j + 1);
+    d.resize(j + 1, 0.0);
+    for (int k = 0; k + 1 < j; ++k) e[k] = off[k];
+    double dk = alpha[0] - mu;
+    bool bad = !(dk < 0.0);
+    for (int k = 1; k < j; ++k) {
+        dk = alpha[k] - mu - off[k - 1] * off[k - 1] / dk;
+        bad = bad || !(dk < 0.0);
+    }
+    ql_first_row(j, d.data(), e.data(), z.data());
+    double tm = d[0], s = 0.0, sc = 0.0;
+    for (int k = 0; k < j; ++k) {
+        tm = std::max(tm, d[k]);
+        s += z[k] * z[k] * std::exp(d[k] - mu);
+        sc += std::exp(d[k] - mu);
+    }
+    *lo = s;
+    if (scales) {
+        scales[0] = sc;
+        scales[1] = 0.0;
+    }
+    if (beta_j < 1e-8) {
+        *hi = s;
+        return 1;
+    }
+    if (bad || tm > mu) {
+        *hi = NAN;
+        return 2;
+    }
+    for (int k = 0; k < j; ++k) d[k] = alpha[k];
+    d[j] = mu + beta_j * beta_j / dk;
+    std::fill(e.begin(), e.end(), 0.0);
+    for (int k = 0; k + 1 < j; ++k) e[k] = off[k];
+    e[j - 1] = beta_j;
+    ql_first_row(j + 1, d.data(), e.data(), z.data());
+    s = sc = 0.0;
+    for (int k = 0; k <= j; ++k) {
+        s += z[k] * z[k] * std::exp(d[k] - mu);
+        sc += std::exp(d[k] - mu);
+    }
+    *hi = s;
+    if (scales) scales[1] = sc;
+    return 0;
+}
+
 }  // namespace kt
 
 // ---------------------------------------------------------------------------
@@ -624,6 +685,22 @@ extern "C" int kt_host_node_update(int j, const double* alpha, const double* off
         return KT_ERR_ARG;
     }
     *xm = kt::node_update_value(j, alpha, off, fun);
+    return KT_OK;
+}
+
+extern "C" int kt_host_gauss_radau(int j, const double* alpha, const double* off, double beta_j, double mu,
+                                   double* lo, double* hi, int* flag) {
+    if (j < 1 || j > kt::kAdaptMaxCap || !alpha || (j > 1 && !off) || !lo || !hi || !flag || !std::isfinite(mu) ||
+        mu > 700.0 || !std::isfinite(beta_j)) {
+        kt::set_error("kt_host_gauss_radau: bad argument (1 <= j <= 256, non-NULL arrays and outputs, finite "
+                      "beta_j, finite mu <= 700)");
+        return KT_ERR_ARG;
+    }
+    double l = 0.0, h = 0.0;
+    *flag = kt::gauss_radau_sums(j, alpha, off, beta_j, mu, &l, &h, nullptr);
+    const double scale = std::exp(mu);
+    *lo = l * scale;
+    *hi = h * scale;
     return KT_OK;
 }
 

@@ -147,7 +147,8 @@ struct ProfSlot {
 // one interval per kt_miobi_break_node step (k_miobi_node_score,
 // k_miobi_node_pick) and per kt_nodes_score_topk scoring launch.  PROF_NODES:
 // kt_trace_fun_update_nodes' own launches, one interval per stopping test
-// (k_node_check, every column group of a depth) and per start (k_unit_start)
+// (k_node_check, every column group of a depth) and per start (k_unit_start);
+// kt_diag_fun_bracket's (k_bracket_check, k_unit_start) report in the same slot
 enum {
     PROF_SPMM = 0, PROF_UPDATE = 1, PROF_START = 2, PROF_YBLOCK = 3, PROF_EXPMV = 4, PROF_FIRST = 5,
     PROF_CHECK = 6, PROF_DIAG = 7, PROF_DIAG_START = 8, PROF_ENTRIES = 9, PROF_EIGS = 10, PROF_MIOBI = 11,
@@ -429,6 +430,13 @@ DepthTest tridiag_depth_test(int j, const double* alpha, const double* off, int 
 // sum |f(eig(T_j))|; tmax (nullable): the largest eigenvalue either sum takes.
 double node_update_value(int j, const double* alpha, const double* off, int fun, double* scale = nullptr,
                          double* tmax = nullptr);
+// The Gauss (lo) and Gauss-Radau (hi, node at mu) sums of exp(A)_ii at depth j
+// from the same tridiagonal, both scaled by exp(-mu); beta_j: the record's next
+// off-diagonal (kt_dense.cpp).  Returns 0 a bracket, 1 beta_j
+// < 1e-8 (hi = lo), 2 mu proved below lambda_max (hi = NaN).  scales (nullable,
+// 2): sum exp(theta_k - mu) over the eigenvalues either sum takes.
+int gauss_radau_sums(int j, const double* alpha, const double* off, double beta_j, double mu, double* lo,
+                     double* hi, double* scales = nullptr);
 bool chol_upper(double* G, int n);
 void tri_upper_inv(const double* R, int n, double* X);
 void sym_eig_host(int n, const double* A, double* w, double* V);

@@ -170,6 +170,15 @@ hipError_t launch_node_check(const double* trec, int mcap, int P, int j, int liv
                              int* active, hipStream_t st);
 hipError_t launch_unit_start(int n, int P, int nc, const int* pos, double* X, double* sc, double* k2s,
                              hipStream_t st);
+// The bracket columns (kt_slq.cpp lanczos_nodes_bracket):
+// launch_node_check's shape and state block for the Gauss / Gauss-Radau bracket
+// of exp(A)_ii with a Radau node at mu; state per column: [0] L_j [1] U_j (both
+// scaled by exp(-mu)) [3] depth [4] stopped [6] flag (0 the gap U_j - L_j <=
+// rtol L_j, 1 beta_j < 1e-8, 2 mu proved below lambda_max, 3 depth mcap
+// reached) [7] last depth.  24 (j + 1) G bytes of LDS: G = P while that fits
+// 64 KB less the static words, else groups of 8.
+hipError_t launch_bracket_check(const double* trec, int mcap, int P, int j, int live, double mu, double rtol,
+                                double* state, int* active, hipStream_t st);
 hipError_t launch_fill(double* x, int count, double v, hipStream_t st);
 hipError_t launch_delay(double microseconds, hipStream_t st);
 // sweep start scales from device column norms (kt_slq.cpp; mode 0 explicit: sc,

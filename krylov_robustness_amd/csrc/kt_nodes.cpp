@@ -8,6 +8,10 @@
 // sweep engine (kt_slq.cpp lanczos_nodes_adaptive; the stopping test is
 // kt_adapt.hip k_node_check).  n <= 130 takes the dense host path, as
 // trace_fun_update.m:37-51 does.
+//
+// kt_diag_fun_bracket (§4.2i) runs the same unit-vector sweeps with the Gauss /
+// Gauss-Radau bracket of exp(A)_ii as their check (lanczos_nodes_bracket,
+// k_bracket_check).
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -99,6 +103,51 @@ extern "C" int kt_trace_fun_update_nodes(kt_matrix_t A, int64_t ncand, const int
         if (!A || (ncand > 0 && (!nodes || !Xm))) fail(KT_ERR_ARG, "kt_trace_fun_update_nodes: NULL argument");
         it = node_checks(A, ncand, nodes, tol, it, "kt_trace_fun_update_nodes");
         nodes_update(A, ncand, nodes, tol, it, fun, Xm, iter, lucky);
+    }
+    KT_NODES_GUARD_END
+}
+
+extern "C" int kt_diag_fun_bracket(kt_matrix_t A, int64_t ncand, const int64_t* nodes, double lam_hi, double rtol,
+                                   int it, double* lo, double* hi, int* iter, int* flag) {
+    try {
+        const std::string w("kt_diag_fun_bracket");
+        if (ncand < 0) fail(KT_ERR_ARG, w + ": negative candidate count");
+        if (it > kAdaptMaxCap) fail(KT_ERR_ARG, w + ": it must be at most 256");
+        if (!std::isfinite(lam_hi) || lam_hi > 700.0)
+            fail(KT_ERR_ARG, w + ": lam_hi must be finite and at most 700 (exp(lam_hi) scales the result)");
+        if (!A || (ncand > 0 && (!nodes || !lo || !hi))) fail(KT_ERR_ARG, w + ": NULL argument");
+        if (A->n > INT32_MAX) fail(KT_ERR_ARG, w + ": n must fit 32-bit indices");
+        for (int64_t c = 0; c < ncand; ++c)
+            if (nodes[c] < 0 || nodes[c] >= A->n) fail(KT_ERR_ARG, w + ": node index out of range");
+        if (A->ctx->ws.slq_submitted != A->ctx->ws.slq_collected)
+            fail(KT_ERR_ARG, w + ": kt_slq_submit calls are outstanding on this context");
+        require_symmetric(A, "DIAG_FUN_BRACKET:: symmetric A required");
+        if (!(rtol > 0.0)) rtol = 1e-10;
+        if (it <= 0) it = (int)std::min<int64_t>(100, A->n);
+        if (ncand == 0) return KT_OK;
+        if (A->n <= 130) {
+            // dense path: exp(A)_ii = sum_k V_ik^2 exp(w_k), on the host
+            const int n = (int)A->n;
+            std::vector<double> D((size_t)n * n, 0.0), wv(n), V((size_t)n * n);
+            for (int r = 0; r < n; ++r)
+                for (int64_t k = A->h_rowptr[r]; k < A->h_rowptr[r + 1]; ++k)
+                    D[r + (size_t)A->h_col[k] * n] = A->h_val[k];
+            sym_eig_host(n, D.data(), wv.data(), V.data());
+            for (int64_t c = 0; c < ncand; ++c) {
+                double s = 0.0;
+                for (int k = 0; k < n; ++k) {
+                    const double v = V[(size_t)nodes[c] + (size_t)k * n];
+                    s += v * v * std::exp(wv[k]);
+                }
+                lo[c] = hi[c] = s;
+                if (iter) iter[c] = 0;
+                if (flag) flag[c] = 0;
+            }
+            return KT_OK;
+        }
+        KT_HIP(hipSetDevice(A->ctx->device));
+        prof_recycle(A->ctx);
+        lanczos_nodes_bracket(A, ncand, nodes, lam_hi, rtol, it, lo, hi, iter, flag);
     }
     KT_NODES_GUARD_END
 }

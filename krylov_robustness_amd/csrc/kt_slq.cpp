@@ -841,8 +841,16 @@ int lanczos_columns_adaptive(kt_matrix_s* A, const double* X, int ldx, int ncols
 // cancellation guard would trip.  The device decides depths; Xm comes from the
 // host QL on the record cut at the column's depth, so a candidate's values
 // depend on (A, node, tol, it, fun) alone.
-void lanczos_nodes_adaptive(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, double tol, int it, int fun,
-                            double* Xm, int* iter, int* lucky) {
+//
+// node_sweeps is that driver with the check as a parameter, shared with the
+// bracket columns (§4.2i): check(record, m, P, j, nc, state, active, stream)
+// queues the stopping test of depth j on a lane; cut(t, d, alpha, off, beta_d)
+// forms column t's values from its record cut at its depth d (alpha: d, off:
+// d - 1 entries, beta_d the record's next off-diagonal), on the host pool.
+namespace {
+
+template <class Check, class Cut>
+void node_sweeps(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, int it, Check check, Cut cut) {
     kt_context_s* ctx = A->ctx;
     const int64_t n = A->n;
     if (ncand < 1) return;
@@ -908,7 +916,7 @@ void lanczos_nodes_adaptive(kt_matrix_s* A, int64_t ncand, const int64_t* nodes,
                 double* dst = ctx->ws.adapt_state[l].as<double>();
                 int* dact = reinterpret_cast<int*>(dst + stw);
                 prof_begin(ctx, PROF_NODES, e.stream(), P);
-                KT_HIP(launch_node_check(e.device_record(), m, P, j + 1, nc, fun, tol, dst, dact, e.stream()));
+                KT_HIP(check(e.device_record(), m, P, j + 1, nc, dst, dact, e.stream()));
                 prof_end(ctx, PROF_NODES, e.stream());
                 if ((j + 1) % kAdaptPoll == 0) {
                     int* word = const_cast<int*>(polled) + 2 * l + (npoll & 1);
@@ -949,14 +957,53 @@ void lanczos_nodes_adaptive(kt_matrix_s* A, int64_t ncand, const int64_t* nodes,
         for (int k = 0; k < d; ++k) al[k] = R[(size_t)k * P + c];
         for (int k = 0; k + 1 < d; ++k)
             off[k] = 0.5 * (R[(size_t)(2 * m + k) * P + c] + R[(size_t)(1 * m + k + 1) * P + c]);
-        Xm[t] = node_update_value(d, al.data(), off.data(), fun);
+        cut(t, d, al.data(), off.data(), R[(size_t)(2 * m + d - 1) * P + c]);
         dep[t] = d;
-        if (iter) iter[t] = d;
-        if (lucky) lucky[t] = R[(size_t)(2 * m + d - 1) * P + c] < 1e-8 ? 1 : 0;
     }, 4);
     ctx->nodes_sweeps = nsw;
     ctx->nodes_steps = steps_queued;
     ctx->nodes_max_depth = *std::max_element(dep.begin(), dep.end());
+}
+
+}  // namespace
+
+void lanczos_nodes_adaptive(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, double tol, int it, int fun,
+                            double* Xm, int* iter, int* lucky) {
+    node_sweeps(
+        A, ncand, nodes, it,
+        [=](const double* trec, int m, int P, int j, int nc, double* state, int* active, hipStream_t st) {
+            return launch_node_check(trec, m, P, j, nc, fun, tol, state, active, st);
+        },
+        [=](int t, int d, const double* al, const double* off, double beta_d) {
+            Xm[t] = node_update_value(d, al, off, fun);
+            if (iter) iter[t] = d;
+            if (lucky) lucky[t] = beta_d < 1e-8 ? 1 : 0;
+        });
+}
+
+// The bracket columns: node_sweeps with k_bracket_check.  The
+// device decides depths; lo / hi come from the host rule (gauss_radau_sums) on
+// the record cut at the column's depth, times exp(mu), and the flag from those
+// values, so a column's results depend on (A, node, mu, rtol, it) alone.
+void lanczos_nodes_bracket(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, double mu, double rtol, int it,
+                           double* lo, double* hi, int* iter, int* flag) {
+    const double scale = std::exp(mu);
+    node_sweeps(
+        A, ncand, nodes, it,
+        [=](const double* trec, int m, int P, int j, int nc, double* state, int* active, hipStream_t st) {
+            return launch_bracket_check(trec, m, P, j, nc, mu, rtol, state, active, st);
+        },
+        [=](int t, int d, const double* al, const double* off, double beta_d) {
+            double l = 0.0, h = 0.0;
+            int f = gauss_radau_sums(d, al, off, beta_d, mu, &l, &h);
+            // the gap is judged on the values returned: a column the device stopped
+            // on a gap the host sums miss by rounding reports 3 below the cap
+            if (f == 0 && !(h - l <= rtol * l)) f = 3;
+            lo[t] = l * scale;
+            hi[t] = h * scale;
+            if (iter) iter[t] = d;
+            if (flag) flag[t] = f;
+        });
 }
 
 static bool pow2_le128(int b) { return b >= 1 && b <= 128 && (b & (b - 1)) == 0; }

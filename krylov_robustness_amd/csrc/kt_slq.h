@@ -250,6 +250,19 @@ int lanczos_columns_adaptive(kt_matrix_s* A, const double* X, int ldx, int ncols
 void lanczos_nodes_adaptive(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, double tol, int it, int fun,
                             double* Xm, int* iter, int* lucky);
 
+// Gauss / Gauss-Radau bracket of exp(A)_ii: for every
+// candidate node i_c (0-based, duplicates legal) lo[c] <= exp(A)_ii <= hi[c]
+// from the same unit-vector sweeps (16 wide, up to four lanes, `it` in 1..256)
+// with kt_adapt.hip k_bracket_check after every step: the Gauss rule of T_j and
+// the Gauss-Radau rule with a node at mu >= lambda_max(A), both scaled by
+// exp(-mu).  A column stops at the first depth whose gap hi - lo <= rtol lo
+// (flag 0), at a beta_j < 1e-8 (1: hi = lo), where mu is proved below
+// lambda_max (2: hi = NaN) or at `it` (3).  lo / hi / flag are formed on the
+// host from the record cut at the column's depth, so they depend on (A, i, mu,
+// rtol, it) only.  iter / flag nullable.  The context's stats 13-15 follow.
+void lanczos_nodes_bracket(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, double mu, double rtol, int it,
+                           double* lo, double* hi, int* iter, int* flag);
+
 // y-form sweep seeded by a device block (see kt_slq.cpp)
 void lanczos_sweep_y_block(kt_matrix_s* A, const DevCSR& M, int P, int m, const double* x, int ldx, int ncols,
                            const double* dnorms2, double* rec_host, int lane);

@@ -632,6 +632,118 @@ def krylov_break_node(A, k, nodes, tol=1e-12, it=None, fun="exp", ctx: Optional[
     return sn[:m] + 1, float(rob.value), D, {"xm": sx[:m].copy()}
 
 
+def lambda_upper(A, rounds=8, ctx: Optional[Context] = None, v=None):
+    """An upper bound on lambda_max of symmetric A, what diag_fun_bracket's
+    lam_hi=None uses.  For an entrywise non-negative A it is rigorous by
+    Collatz-Wielandt: lambda_max <= max_i (A x)_i / x_i for any x > 0.  x starts
+    at |v| + 1e-3 max|v| with v the leading eigenvector of eigs_leading (or the
+    given v, and then no device is touched) and takes `rounds` steps x <- (A +
+    I) x, normalised, none of which can raise the bound; the result is the
+    smaller of that and ||A||_inf.  A matrix with a negative entry gets
+    ||A||_inf.  Host numpy on the exported CSR; multiplied by 1 + 1e-12 so that
+    rounding cannot put it below lambda_max."""
+    import scipy.sparse as sp
+    M = sp.csr_matrix(A.to_scipy() if isinstance(A, DeviceMatrix) else A, dtype=np.float64)
+    n = M.shape[0]
+    slack = 1.0 + 1e-12
+    norm_inf = float(abs(M).sum(axis=1).max()) if M.nnz else 0.0
+    if n == 0 or M.nnz == 0 or M.data.min() < 0.0:
+        return norm_inf * slack
+    if v is None:
+        from .core import eigs_leading
+        v = eigs_leading(A, ctx=ctx)[1]
+    x = np.abs(np.asarray(v, dtype=np.float64).ravel())
+    if x.size != n or not np.all(np.isfinite(x)) or x.max() <= 0.0:
+        x = np.ones(n)
+    x = x + 1e-3 * x.max()
+    bound = norm_inf
+    for r in range(int(rounds) + 1):
+        y = M @ x
+        bound = min(bound, float(np.max(y / x)))
+        if r < int(rounds):
+            x = y + x
+            x /= x.max()
+    return bound * slack
+
+
+def diag_fun_bracket(A, nodes, rtol=1e-10, it=None, lam_hi=None, ctx: Optional[Context] = None):
+    """Proved bounds lo[c] <= exp(A)_ii <= hi[c] on the subgraph centrality of
+    every node i of `nodes` (1-based, as trace_fun_update_nodes'; duplicates are
+    legal): the Gauss and Gauss-Radau rules of the Lanczos run started at e_i
+    (kt_diag_fun_bracket), each column run until hi - lo <=
+    rtol lo.  lam_hi must be an upper bound on lambda_max(A) (None:
+    lambda_upper(A)); the upper bounds are proved only if it is one.  f = exp
+    only.  A candidate's values do not depend on the other candidates of the
+    call.  Returns (lo, hi, iter, flag) arrays; flag 0: the gap was reached, 1:
+    the Krylov space ended, hi = lo is exact, 2: lam_hi is proved to be below
+    lambda_max, lo holds and hi is NaN, 3: `it` steps (None: min(100, n); at
+    most 256) did not reach the gap, the bracket is still valid."""
+    who = "diag_fun_bracket"
+    if it is not None and int(it) > 256:
+        raise _lib.KrylovError(_lib.KT_ERR_ARG, f"{who}: it must be at most 256")
+    nd = np.asarray(nodes, dtype=np.int64).ravel() - 1
+    n = A.n if isinstance(A, DeviceMatrix) else A.shape[0]
+    if nd.size and (nd.min() < 0 or nd.max() >= n):
+        raise _lib.KrylovError(_lib.KT_ERR_ARG, f"{who}: node index out of range (1-based, 1..{n})")
+    if lam_hi is not None and not (np.isfinite(lam_hi) and float(lam_hi) <= 700.0):
+        raise _lib.KrylovError(_lib.KT_ERR_ARG, f"{who}: lam_hi must be finite and at most 700")
+    D = _dev(A, ctx)
+    if lam_hi is None:
+        # n <= 130 takes the dense host path, which has no use for a Radau node
+        lam_hi = lambda_upper(D, ctx=ctx) if n > 130 else 0.0
+    q = nd.size
+    nd, pn = _i64(nd)
+    lo = np.zeros(max(q, 1))
+    hi = np.zeros(max(q, 1))
+    itr = np.zeros(max(q, 1), dtype=np.int32)
+    fl = np.zeros(max(q, 1), dtype=np.int32)
+    _lib.check(_lib.load().kt_diag_fun_bracket(
+        D.handle, q, pn, float(lam_hi), float(rtol), int(it or 0), _dptr(lo), _dptr(hi),
+        itr.ctypes.data_as(C.POINTER(C.c_int)), fl.ctypes.data_as(C.POINTER(C.c_int))))
+    return lo[:q], hi[:q], itr[:q], fl[:q]
+
+
+def find_top_nodes_fun(A, num, ncand=None, nprobes=256, deflate=1, rtol=1e-10, m=30, seed=0, it=None, lam_hi=None,
+                       fun="exp", ctx: Optional[Context] = None):
+    """The top `num` nodes by subgraph centrality exp(A)_ii with a proved order
+    among the candidates: rank all nodes by the stochastic estimate
+    diag_fun(A, nprobes, m, seed, deflate=deflate).mean, bracket the first
+    `ncand` of that ranking (default 4 num) with diag_fun_bracket(rtol, it,
+    lam_hi) and return the first `num` of them by descending lower bound, ties
+    by index; 1-based.
+
+    Returns (nodes, info): info "candidates" (1-based, in the bracketed order:
+    descending lo, ties by index), "lo" and "hi" in that order, and "separated":
+    True when every lo[r] > hi[r + 1] over all bracketed candidates, so their
+    order is proved.  That proof covers the candidate set only: a node the
+    stochastic ranking left out of it is bounded by nothing here, and may
+    belong among the returned ones.  With the defaults that happens: 256 probes
+    leave the estimate several per cent off per node, so where the top nodes
+    are nearly tied (rome: the fifth is 0.05 % above the sixth) a true top node
+    can be missing from the 4 num candidates; raise nprobes and ncand until the
+    candidate set holds every node within a few standard errors
+    (diag_fun(...).stderr) of the num-th value.  f = exp only: the bracket needs every
+    derivative of f positive, which cosh, sinh and the other kt_fun codes do
+    not give for a single Radau node."""
+    if _fun_code(fun) != _lib.FUN_CODES["exp"]:
+        raise _lib.KrylovError(_lib.KT_ERR_ARG, "find_top_nodes_fun: only fun = exp is supported (the Gauss / "
+                                                "Gauss-Radau bracket needs every derivative of f positive)")
+    from .core import diag_fun
+    D = _dev(A, ctx)
+    n, _ = D.info()
+    num = int(np.floor(num))
+    if n < num:
+        raise IndexError("FIND_TOP_NODES:: there are not enough nodes in the graph")
+    ncand = min(n, max(num, 4 * num if ncand is None else int(ncand)))
+    est = diag_fun(D, nprobes, m=m, seed=seed, fun="exp", deflate=deflate, ctx=D.ctx).mean
+    cand = _stable_head(-est, ncand)
+    lo, hi, _, _ = diag_fun_bracket(D, cand + 1, rtol=rtol, it=it, lam_hi=lam_hi, ctx=D.ctx)
+    order = np.lexsort((cand, -lo))
+    cand, lo, hi = cand[order], lo[order], hi[order]
+    separated = bool(np.all(lo[:-1] > hi[1:])) if ncand > 1 else True
+    return cand[:num] + 1, {"lo": lo, "hi": hi, "candidates": cand + 1, "separated": separated}
+
+
 def find_top_nodes_miobi(A, num, t=25, tol=0.0, max_spmm=0, seed=0, ctx: Optional[Context] = None):
     """The top `num` nodes ranked by ascending MIOBI node score (the node
     miobi_break_node would remove first comes first) from the leading t

@@ -632,6 +632,46 @@ int kt_diag_fun_bracket(kt_matrix_t A, int64_t ncand, const int64_t* nodes, doub
 int kt_host_gauss_radau(int j, const double* alpha, const double* off, double beta_j, double mu, double* lo,
                         double* hi, int* flag);
 
+/* Proved bounds on communicability.  For every pair (ei[p],
+ * ej[p]) (0-based, i != j; repeats are legal) lo[p] <= exp(A)_ij <= hi[p].  With
+ * z+- = e_i +- e_j and g+- = (z+- / sqrt 2)' exp(A) (z+- / sqrt 2), exp(A)_ij =
+ * (g+ - g-) / 2; each g is a quadratic form of exp, bracketed as
+ * kt_diag_fun_bracket brackets exp(A)_ii by the Gauss rule L and the
+ * Gauss-Radau rule U of the Lanczos run started at z+- / sqrt 2, so
+ *   lo = (L+ - U-) / 2,  hi = (U+ - L-) / 2.
+ * A pair is canonicalised to (min, max) first: (i, j) and (j, i) return the
+ * same bits.  It takes two adjacent columns of kt_diag_fun_bracket's sweeps (8
+ * pairs a sweep); at every depth j, in this order:
+ *   a column whose own beta_j < 1e-8 becomes exact (U := L) and is frozen at
+ *           depth j while the other one goes on;
+ *   flag 2: a running column proves lam_hi below lambda_max(A) (a pivot d_k >=
+ *           0 or a Ritz value above lam_hi): lo = hi = NaN;
+ *   flag 1: both columns are frozen: lo = hi;
+ *   flag 0: lo hi > 0 and 0 <= hi - lo <= rtol min(|lo|, |hi|);
+ *   flag 4: hi - lo <= ftol (U+ + U-) / 2 -- the bracket has closed to the
+ *           rounding level of the two quadratic forms, whose size is that of
+ *           (exp(A)_ii + exp(A)_jj) / 2, and the entry lies below what the
+ *           method resolves; such a bracket can come out inverted (hi < lo) by
+ *           a few ulps of that scale;
+ *   flag 3: j = it, the last bracket, still a valid one.
+ * The device decides depths only; lo, hi and flag come from the host rule on
+ * each column's record cut at that column's depth (col_iter, 2 per pair: the +
+ * and the - column; iter is the larger), the flag judged on the values
+ * returned: a device flag 0 that they miss by rounding falls to 4 or 3.  So a
+ * pair's results depend on (A, i, j, lam_hi, rtol, ftol, it) only -- not on what
+ * shares its sweep or its call -- bit for bit.  The sums are formed scaled by
+ * exp(-lam_hi) and multiplied by exp(lam_hi) once.  rtol <= 0: 1e-10.  ftol <=
+ * 0: 1e-12.  it <= 0: min(100, n).  iter, flag (npairs each) and col_iter (2
+ * npairs) are nullable.  n <= 130 takes the dense host path (lo = hi = the
+ * entry from one eigendecomposition), iter = 0, flag = 0.  f = exp only.
+ * KT_ERR_ARG before the device is touched for NULL arguments, an index outside
+ * 0..n-1, a pair with i == j (kt_diag_fun_bracket bounds those), it > 256, a
+ * lam_hi that is not finite or above 700, or outstanding kt_slq_submit calls;
+ * KT_ERR_NOT_HERMITIAN for non-symmetric A. */
+int kt_entries_fun_bracket(kt_matrix_t A, int64_t npairs, const int64_t* ei, const int64_t* ej, double lam_hi,
+                           double rtol, double ftol, int it, double* lo, double* hi, int* iter, int* flag,
+                           int* col_iter);
+
 /* Per-kernel timing (HIP events recorded on the library's stream around each
  * launch of the named kernel while enabled).  kernel: 0 = the probe-Lanczos
  * gather pass (k_spmm_lanczos in the y-form sweep, k_spmm_dot = K1 in the
@@ -662,7 +702,8 @@ int kt_host_gauss_radau(int j, const double* alpha, const double* off, double be
  * 14 = kt_trace_fun_update_nodes' own launches: the stopping tests
  * (k_node_check, one interval per sweep and depth) and the unit-vector starts
  * (k_unit_start); its sweeps' passes report in 0 and 1.  kt_diag_fun_bracket's
- * (k_bracket_check, k_unit_start) report here too.
+ * (k_bracket_check, k_unit_start) and kt_entries_fun_bracket's
+ * (k_pair_bracket_check, k_pair_start) report here too.
  * Returns launch count and summed milliseconds. */
 int kt_profile_enable(kt_context_t ctx, int enable);
 int kt_profile_read(kt_context_t ctx, int kernel, int64_t* launches, double* total_ms);
@@ -707,7 +748,7 @@ int kt_debug_delay(kt_context_t ctx, int lane, double microseconds);
  * kt_miobi_break_node: those and the window's row lists); its edits of A.
  * stats 13, 14, 15: of the last
  * kt_trace_fun_update_nodes call on this context (kt_krylov_break_node: of its
- * last greedy step) or kt_diag_fun_bracket call -- its sweeps, the sweep steps
+ * last greedy step), kt_diag_fun_bracket or kt_entries_fun_bracket call -- its sweeps, the sweep steps
  * it queued (one SpMM pass over A each) and the depth of its deepest column. */
 int kt_context_stat(kt_context_t ctx, int stat, int64_t* value);
 

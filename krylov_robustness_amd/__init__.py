@@ -20,7 +20,8 @@ from .greedy import (compute_centrality, default_greedy_tol, edge2low_rank, find
                      find_top_edges_fun, find_top_edges_miobi, find_top_missing_edges, find_top_nodes_miobi,
                      greedy_krylov, krylov_miobi, krylov_miobi_sharded, miobi_break, miobi_break_node, miobi_loop,
                      miobi_make, nodes_score_topk, pairs_score_topk, select_extreme, trace_fun_update_pairs,
-                     krylov_break_node, trace_fun_update_nodes, diag_fun_bracket, find_top_nodes_fun, lambda_upper)
+                     krylov_break_node, trace_fun_update_nodes, diag_fun_bracket, find_top_nodes_fun, lambda_upper,
+                     entries_fun_bracket, find_top_edges_bracket)
 from . import datasets, matv73
 from .dist import mc_trace_sharded, trace_exp_sharded
 from .datasets import load_problem, load_unweighted, prepare_unweighted, prepare_weighted
@@ -39,4 +40,5 @@ __all__ = [
     "mc_trace_sharded", "trace_exp_sharded", "edge2low_rank", "pairs_score_topk", "miobi_break", "miobi_make",
     "find_top_edges_miobi", "miobi_break_node", "nodes_score_topk", "find_top_nodes_miobi",
     "trace_fun_update_nodes", "krylov_break_node", "diag_fun_bracket", "find_top_nodes_fun", "lambda_upper",
+    "entries_fun_bracket", "find_top_edges_bracket",
 ]

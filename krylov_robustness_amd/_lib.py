@@ -126,6 +126,8 @@ SIGNATURES = [
     ("kt_host_node_update", C.c_int, [C.c_int, _dp, _dp, C.c_int, _dp]),
     ("kt_diag_fun_bracket", C.c_int, [_mat_p, C.c_int64, _i64p, C.c_double, C.c_double, C.c_int, _dp, _dp, _ip,
                                       _ip]),
+    ("kt_entries_fun_bracket", C.c_int, [_mat_p, C.c_int64, _i64p, _i64p, C.c_double, C.c_double, C.c_double,
+                                         C.c_int, _dp, _dp, _ip, _ip, _ip]),
     ("kt_host_gauss_radau", C.c_int, [C.c_int, _dp, _dp, C.c_double, C.c_double, _dp, _dp, _ip]),
     ("kt_profile_enable", C.c_int, [_ctx_p, C.c_int]),
     ("kt_profile_read", C.c_int, [_ctx_p, C.c_int, _i64p, _dp]),

@@ -6,7 +6,9 @@
 // the host from the record truncated at the depth chosen here.
 // k_node_check is the same for the node-removal columns of
 // lanczos_nodes_adaptive (§4.2h), k_unit_start their sweeps' start block, and
-// k_bracket_check the test of lanczos_nodes_bracket's columns (§4.2i).
+// k_bracket_check the test of lanczos_nodes_bracket's columns (§4.2i);
+// k_pair_bracket_check and k_pair_start are the same for the column pairs of
+// lanczos_pairs_bracket (§4.2j).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -432,6 +434,59 @@ hipError_t launch_node_check(const double* trec, int mcap, int P, int j, int liv
     return hipSuccess;
 }
 
+// One column's Gauss / Gauss-Radau sums at depth j, the body k_bracket_check and
+// k_pair_bracket_check share (lane t of G owns column c; sm: the three LDS
+// arrays): *lo = L_j, *hi = U_j.  Returns 1 when beta_j < 1e-8 (*hi = *lo), 2
+// when a pivot is not negative or a Ritz value lies above mu (*hi = NaN), else 0.
+__device__ __forceinline__ int dev_bracket_column(const double* __restrict__ trec, int mcap, int P, int j, int c,
+                                                  int t, int G, double mu, double* sm, double* plo, double* phi) {
+    const double* al = trec + c;
+    const double* up = trec + (size_t)mcap * P + c;
+    const double* low = trec + (size_t)2 * mcap * P + c;
+    double* d = sm + t;
+    double* e = sm + (size_t)(j + 1) * G + t;
+    double* z = sm + (size_t)2 * (j + 1) * G + t;
+    double dk = al[0] - mu;
+    bool bad = !(dk < 0.0);
+    d[0] = al[0];
+    for (int k = 1; k < j; ++k) {
+        const double b = 0.5 * (low[(size_t)(k - 1) * P] + up[(size_t)k * P]);
+        e[(k - 1) * G] = b;
+        d[k * G] = al[(size_t)k * P];
+        dk = al[(size_t)k * P] - mu - b * b / dk;
+        bad = bad || !(dk < 0.0);
+    }
+    dev_ql_rows<false>(j, G, d, e, z, nullptr);
+    double tm = d[0], lo = 0.0;
+    for (int k = 0; k < j; ++k) {
+        tm = fmax(tm, d[k * G]);
+        lo += z[k * G] * z[k * G] * exp(d[k * G] - mu);
+    }
+    const double bj = low[(size_t)(j - 1) * P];
+    double hi = lo;
+    int kind = 0;
+    if (bj < 1e-8) {
+        kind = 1;
+    } else if (bad || tm > mu) {
+        kind = 2;
+        hi = NAN;
+    } else {
+        d[0] = al[0];
+        for (int k = 1; k < j; ++k) {
+            e[(k - 1) * G] = 0.5 * (low[(size_t)(k - 1) * P] + up[(size_t)k * P]);
+            d[k * G] = al[(size_t)k * P];
+        }
+        e[(j - 1) * G] = bj;
+        d[j * G] = mu + bj * bj / dk;
+        dev_ql_rows<false>(j + 1, G, d, e, z, nullptr);
+        hi = 0.0;
+        for (int k = 0; k <= j; ++k) hi += z[k * G] * z[k * G] * exp(d[k * G] - mu);
+    }
+    *plo = lo;
+    *phi = hi;
+    return kind;
+}
+
 // The stopping test of a bracket column at depth j (kt_slq.cpp
 // lanczos_nodes_bracket): k_node_check's launch shape and state block -- one
 // wavefront, lane t owns column c = g0 + t (t < G, c < live), LDS arrays
@@ -461,47 +516,10 @@ __global__ __launch_bounds__(64) void k_bracket_check(const double* __restrict__
         double* st = state + (size_t)c * kAdaptState;
         stopped = st[4] != 0.0;
         if (!stopped) {
-            const double* al = trec + c;
-            const double* up = trec + (size_t)mcap * P + c;
-            const double* low = trec + (size_t)2 * mcap * P + c;
-            double* d = sm + t;
-            double* e = sm + (size_t)(j + 1) * G + t;
-            double* z = sm + (size_t)2 * (j + 1) * G + t;
-            double dk = al[0] - mu;
-            bool bad = !(dk < 0.0);
-            d[0] = al[0];
-            for (int k = 1; k < j; ++k) {
-                const double b = 0.5 * (low[(size_t)(k - 1) * P] + up[(size_t)k * P]);
-                e[(k - 1) * G] = b;
-                d[k * G] = al[(size_t)k * P];
-                dk = al[(size_t)k * P] - mu - b * b / dk;
-                bad = bad || !(dk < 0.0);
-            }
-            dev_ql_rows<false>(j, G, d, e, z, nullptr);
-            double tm = d[0], lo = 0.0;
-            for (int k = 0; k < j; ++k) {
-                tm = fmax(tm, d[k * G]);
-                lo += z[k * G] * z[k * G] * exp(d[k * G] - mu);
-            }
-            const double bj = low[(size_t)(j - 1) * P];
-            double hi = lo;
-            int flag = -1;
-            if (bj < 1e-8) {
-                flag = 1;
-            } else if (bad || tm > mu) {
-                flag = 2;
-                hi = NAN;
-            } else {
-                d[0] = al[0];
-                for (int k = 1; k < j; ++k) {
-                    e[(k - 1) * G] = 0.5 * (low[(size_t)(k - 1) * P] + up[(size_t)k * P]);
-                    d[k * G] = al[(size_t)k * P];
-                }
-                e[(j - 1) * G] = bj;
-                d[j * G] = mu + bj * bj / dk;
-                dev_ql_rows<false>(j + 1, G, d, e, z, nullptr);
-                hi = 0.0;
-                for (int k = 0; k <= j; ++k) hi += z[k * G] * z[k * G] * exp(d[k * G] - mu);
+            double lo, hi;
+            const int kind = dev_bracket_column(trec, mcap, P, j, c, t, G, mu, sm, &lo, &hi);
+            int flag = kind ? kind : -1;
+            if (!kind) {
                 if (hi - lo <= rtol * lo)
                     flag = 0;
                 else if (j == mcap)
@@ -550,6 +568,123 @@ hipError_t launch_bracket_check(const double* trec, int mcap, int P, int j, int 
     return hipSuccess;
 }
 
+// The stopping test of a pair's two bracket columns at depth j (DESIGN.md §4.2j;
+// kt_slq.cpp lanczos_pairs_bracket): k_bracket_check's launch shape, LDS layout
+// and state block.  Columns 2p and 2p + 1 are the Lanczos runs started at
+// (e_i + e_j) / sqrt 2 and (e_i - e_j) / sqrt 2 of pair p; live, g0 and G are
+// even, so both sit in one launch, in neighbouring lanes.  With L, U the Gauss
+// and Gauss-Radau sums of the two columns (dev_bracket_column, scaled by
+// exp(-mu)), lo = (L+ - U-) / 2 <= exp(A)_ij exp(-mu) <= hi = (U+ - L-) / 2.
+// state per column:
+//   [0] L  [1] U  [3] depth  [4] stopped  [5] the pair is decided
+//   [6] flag: 1 while the column is frozen and its pair undecided, then the pair's
+//   [7] the depth of the column's last check
+// A column whose beta_j < 1e-8 is frozen at j (stopped, U := L, its depth and
+// sums kept) while the other one runs on.  Then, in this order: flag 2 when a
+// running column proves mu below lambda_max, 1 when both are frozen, 0 when
+// lo hi > 0 and 0 <= hi - lo <= rtol min(|lo|, |hi|), 4 when hi - lo <= ftol
+// (U+ + U-) / 2, the rounding level of the two sums (an inverted bracket too), 3
+// at j = mcap.  A decided pair stops its running columns at j and is left as it
+// is from then on.  The lanes hand their sums over through the QL arrays'
+// first 3 G words once every lane is done with them.  active[0]: as
+// k_quad_check's.
+__global__ __launch_bounds__(64) void k_pair_bracket_check(const double* __restrict__ trec, int mcap, int P, int j,
+                                                           int live, int g0, int G, double mu, double rtol,
+                                                           double ftol, double* __restrict__ state,
+                                                           int* __restrict__ active) {
+    extern __shared__ double sm[];
+    __shared__ int stopped_l[64];
+    const int t = threadIdx.x, c = g0 + t;
+    const bool mine = t < G && c < live;
+    double* st = state + (size_t)(mine ? c : 0) * kAdaptState;
+    int kind = -1;  // -1: no column here, or its pair is decided; 0 a bracket; 1 frozen; 2 mu too small
+    double lo = 0.0, hi = 0.0;
+    if (mine && st[5] == 0.0) {
+        if (st[4] != 0.0) {
+            kind = 1;
+            lo = st[0];
+            hi = st[1];
+        } else {
+            kind = dev_bracket_column(trec, mcap, P, j, c, t, G, mu, sm, &lo, &hi);
+            st[0] = lo;
+            st[1] = hi;
+            st[7] = (double)j;
+            if (kind == 1) {
+                st[3] = (double)j;
+                st[4] = 1.0;
+                st[6] = 1.0;
+            }
+        }
+    }
+    __syncthreads();  // every lane is done with its QL arrays
+    if (t < G) {
+        sm[t] = lo;
+        sm[G + t] = hi;
+        sm[2 * G + t] = (double)kind;
+    }
+    __syncthreads();
+    int stopped = -1;
+    if (mine) {
+        if (kind >= 0) {
+            const int a = t & ~1;  // the pair's + column; a + 1 < G: g0, G and live are even
+            const double Lp = sm[a], Up = sm[G + a], Lm = sm[a + 1], Um = sm[G + a + 1];
+            const int kp = (int)sm[2 * G + a], km = (int)sm[2 * G + a + 1];
+            int flag = -1;
+            if (kp == 2 || km == 2) {
+                flag = 2;
+            } else if (kp == 1 && km == 1) {
+                flag = 1;
+            } else {
+                const double plo = 0.5 * (Lp - Um), phi = 0.5 * (Up - Lm), gap = phi - plo;
+                if (plo * phi > 0.0 && gap >= 0.0 && gap <= rtol * fmin(fabs(plo), fabs(phi)))
+                    flag = 0;
+                else if (gap <= ftol * (0.5 * (Up + Um)))
+                    flag = 4;
+                else if (j == mcap)
+                    flag = 3;
+            }
+            if (flag >= 0) {
+                st[5] = 1.0;
+                st[6] = (double)flag;
+                if (st[4] == 0.0) {
+                    st[3] = (double)j;
+                    st[4] = 1.0;
+                }
+            }
+        }
+        stopped = st[4] != 0.0;
+    }
+    stopped_l[t] = stopped;
+    __syncthreads();
+    if (t == 0) {
+        int run = 0;
+        for (int k = 0; k < live; ++k) {
+            const bool here = k >= g0 && k < g0 + G;  // another group's columns: an earlier launch wrote them
+            run += here ? (stopped_l[k - g0] == 0) : (state[(size_t)k * kAdaptState + 4] == 0.0);
+        }
+        active[0] = run;
+    }
+}
+
+// launch_bracket_check's shapes and groups, P and live even: G = P or 8, so a
+// group holds whole pairs.
+hipError_t launch_pair_bracket_check(const double* trec, int mcap, int P, int j, int live, double mu, double rtol,
+                                     double ftol, double* state, int* active, hipStream_t st) {
+    if (P < 2 || P > 32 || (P & 1) || live < 2 || live > P || (live & 1) || j < 1 || j > mcap || mcap > 256)
+        return hipErrorInvalidValue;
+    const size_t room = (size_t)65536 - 512;
+    const size_t per_lane = sizeof(double) * 3 * (size_t)(j + 1);
+    const int G = (per_lane * P <= room) ? P : 8;
+    if (per_lane * G > room) return hipErrorInvalidValue;
+    for (int g0 = 0; g0 < live; g0 += G) {
+        k_pair_bracket_check<<<1, 64, per_lane * G, st>>>(trec, mcap, P, j, live, g0, G, mu, rtol, ftol, state,
+                                                          active);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // The start of a node-removal sweep: column c < nc of the zeroed n x P block X
 // gets 1 at row pos[c] (the candidate's row in the sweep's row order; duplicate
 // rows are legal, each in its own column), and the sweep's start scale and
@@ -570,6 +705,34 @@ hipError_t launch_unit_start(int n, int P, int nc, const int* pos, double* X, do
                              hipStream_t st) {
     if (n < 1 || P < 1 || P > 64 || nc < 0 || nc > P) return hipErrorInvalidValue;
     k_unit_start<<<1, 64, 0, st>>>(n, P, nc, pos, X, sc, k2s);
+    return hipGetLastError();
+}
+
+// The start of a pair sweep: pair p < np of the zeroed n x P
+// block X gets e_i + e_j in column 2p and e_i - e_j in column 2p + 1, i =
+// pos[2p], j = pos[2p + 1] the pair's rows in the sweep's row order (i != j;
+// repeated pairs are legal, each in its own two columns).  The start scale is
+// 1 / sqrt 2 and the squared norm 2 for those columns, 0 for the padding.
+__global__ __launch_bounds__(64) void k_pair_start(int n, int P, int np, const int* __restrict__ pos,
+                                                   double* __restrict__ X, double* __restrict__ sc,
+                                                   double* __restrict__ k2s) {
+    const int c = threadIdx.x;
+    if (c >= P) return;
+    const int p = c >> 1;
+    const int ri = p < np ? pos[2 * p] : -1, rj = p < np ? pos[2 * p + 1] : -1;
+    const bool ok = ri >= 0 && ri < n && rj >= 0 && rj < n && ri != rj;
+    if (ok) {
+        X[(size_t)ri * P + c] = 1.0;
+        X[(size_t)rj * P + c] = (c & 1) ? -1.0 : 1.0;
+    }
+    sc[c] = ok ? 0.70710678118654752440 : 0.0;
+    k2s[c] = ok ? 2.0 : 0.0;
+}
+
+hipError_t launch_pair_start(int n, int P, int np, const int* pos, double* X, double* sc, double* k2s,
+                             hipStream_t st) {
+    if (n < 2 || P < 2 || P > 64 || (P & 1) || np < 0 || 2 * np > P) return hipErrorInvalidValue;
+    k_pair_start<<<1, 64, 0, st>>>(n, P, np, pos, X, sc, k2s);
     return hipGetLastError();
 }
 

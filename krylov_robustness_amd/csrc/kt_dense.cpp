@@ -313,6 +313,28 @@ int gauss_radau_sums(int j, const double* alpha, const double* off, double beta_
     return 0;
 }
 
+// exp(A)_ij = (g+ - g-) / 2 with g+- the quadratic forms of exp at (e_i +- e_j)
+// / sqrt 2: their brackets [Lp, Up] and [Lm, Um] give lo = (Lp - Um) / 2 <=
+// exp(A)_ij <= hi = (Up - Lm) / 2.  The flag is judged on
+// these values, in kt_entries_fun_bracket's order.  The floor: both sums carry
+// rounding errors of the size of (Up + Um) / 2 eps, so a gap at ftol of that is
+// all the method resolves -- an entry far below the two diagonal ones, whose
+// bracket may even come out inverted by a few ulps of that scale.
+int pair_bracket_combine(double Lp, double Up, int kp, double Lm, double Um, int km, double rtol, double ftol,
+                         double* lo, double* hi) {
+    if (kp == 2 || km == 2) {
+        *lo = *hi = NAN;
+        return 2;
+    }
+    const double l = 0.5 * (Lp - Um), h = 0.5 * (Up - Lm), gap = h - l;
+    *lo = l;
+    *hi = h;
+    if (kp == 1 && km == 1) return 1;
+    if (l * h > 0.0 && gap >= 0.0 && gap <= rtol * std::min(std::fabs(l), std::fabs(h))) return 0;
+    if (gap <= ftol * (0.5 * (Up + Um))) return 4;
+    return 3;
+}
+
 }  // namespace kt
 
 // ---------------------------------------------------------------------------

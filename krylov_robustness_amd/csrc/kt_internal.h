@@ -148,7 +148,8 @@ struct ProfSlot {
 // k_miobi_node_pick) and per kt_nodes_score_topk scoring launch.  PROF_NODES:
 // kt_trace_fun_update_nodes' own launches, one interval per stopping test
 // (k_node_check, every column group of a depth) and per start (k_unit_start);
-// kt_diag_fun_bracket's (k_bracket_check, k_unit_start) report in the same slot
+// kt_diag_fun_bracket's (k_bracket_check, k_unit_start) and
+// kt_entries_fun_bracket's (k_pair_bracket_check, k_pair_start) report in the same slot
 enum {
     PROF_SPMM = 0, PROF_UPDATE = 1, PROF_START = 2, PROF_YBLOCK = 3, PROF_EXPMV = 4, PROF_FIRST = 5,
     PROF_CHECK = 6, PROF_DIAG = 7, PROF_DIAG_START = 8, PROF_ENTRIES = 9, PROF_EIGS = 10, PROF_MIOBI = 11,
@@ -437,6 +438,14 @@ double node_update_value(int j, const double* alpha, const double* off, int fun,
 // 2): sum exp(theta_k - mu) over the eigenvalues either sum takes.
 int gauss_radau_sums(int j, const double* alpha, const double* off, double beta_j, double mu, double* lo,
                      double* hi, double* scales = nullptr);
+// The bracket of exp(A)_ij from the sums of its two columns, started at (e_i +
+// e_j) / sqrt 2 (Lp, Up, kp) and (e_i - e_j) / sqrt 2 (Lm, Um, km), k the value
+// gauss_radau_sums returned (kt_dense.cpp): *lo = (Lp - Um) /
+// 2, *hi = (Up - Lm) / 2.  Returns 2 when either k is 2 (*lo = *hi = NaN), 1
+// when both are 1, 0 when lo hi > 0 and 0 <= hi - lo <= rtol min(|lo|, |hi|), 4
+// when hi - lo <= ftol (Up + Um) / 2, else 3.
+int pair_bracket_combine(double Lp, double Up, int kp, double Lm, double Um, int km, double rtol, double ftol,
+                         double* lo, double* hi);
 bool chol_upper(double* G, int n);
 void tri_upper_inv(const double* R, int n, double* X);
 void sym_eig_host(int n, const double* A, double* w, double* V);

@@ -179,6 +179,21 @@ hipError_t launch_unit_start(int n, int P, int nc, const int* pos, double* X, do
 // 64 KB less the static words, else groups of 8.
 hipError_t launch_bracket_check(const double* trec, int mcap, int P, int j, int live, double mu, double rtol,
                                 double* state, int* active, hipStream_t st);
+// The pair columns (kt_slq.cpp lanczos_pairs_bracket): columns
+// 2p, 2p + 1 of a sweep are pair p's runs started at (e_i +- e_j) / sqrt 2.
+// launch_pair_start: launch_unit_start for them, pos[2p], pos[2p + 1] the
+// pair's rows (np pairs, 2 np <= P, P even), sc = 1 / sqrt 2 and k2s = 2 for
+// live columns.  launch_pair_bracket_check: launch_bracket_check's shape (P and
+// live even, groups of P or 8 lanes hold whole pairs) for the bracket lo = (L+
+// - U-) / 2, hi = (U+ - L-) / 2 of exp(A)_ij; state per column: [0] L [1] U
+// [3] depth [4] stopped [5] the pair is decided [6] flag (1 a frozen column of
+// an undecided pair; then the pair's: 0 the gap <= rtol min(|lo|, |hi|) with lo
+// hi > 0, 1 both columns frozen, 2 mu proved below lambda_max, 3 depth mcap
+// reached, 4 the gap <= ftol (U+ + U-) / 2) [7] last depth.
+hipError_t launch_pair_start(int n, int P, int np, const int* pos, double* X, double* sc, double* k2s,
+                             hipStream_t st);
+hipError_t launch_pair_bracket_check(const double* trec, int mcap, int P, int j, int live, double mu, double rtol,
+                                     double ftol, double* state, int* active, hipStream_t st);
 hipError_t launch_fill(double* x, int count, double v, hipStream_t st);
 hipError_t launch_delay(double microseconds, hipStream_t st);
 // sweep start scales from device column norms (kt_slq.cpp; mode 0 explicit: sc,

@@ -11,7 +11,9 @@
 //
 // kt_diag_fun_bracket (§4.2i) runs the same unit-vector sweeps with the Gauss /
 // Gauss-Radau bracket of exp(A)_ii as their check (lanczos_nodes_bracket,
-// k_bracket_check).
+// k_bracket_check); kt_entries_fun_bracket (§4.2j) brackets exp(A)_ij from two
+// such columns per pair, started at (e_i +- e_j) / sqrt 2 (lanczos_pairs_bracket,
+// k_pair_start, k_pair_bracket_check).
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -148,6 +150,63 @@ extern "C" int kt_diag_fun_bracket(kt_matrix_t A, int64_t ncand, const int64_t* 
         KT_HIP(hipSetDevice(A->ctx->device));
         prof_recycle(A->ctx);
         lanczos_nodes_bracket(A, ncand, nodes, lam_hi, rtol, it, lo, hi, iter, flag);
+    }
+    KT_NODES_GUARD_END
+}
+
+extern "C" int kt_entries_fun_bracket(kt_matrix_t A, int64_t npairs, const int64_t* ei, const int64_t* ej,
+                                      double lam_hi, double rtol, double ftol, int it, double* lo, double* hi,
+                                      int* iter, int* flag, int* col_iter) {
+    try {
+        const std::string w("kt_entries_fun_bracket");
+        if (npairs < 0) fail(KT_ERR_ARG, w + ": negative pair count");
+        if (it > kAdaptMaxCap) fail(KT_ERR_ARG, w + ": it must be at most 256");
+        if (!std::isfinite(lam_hi) || lam_hi > 700.0)
+            fail(KT_ERR_ARG, w + ": lam_hi must be finite and at most 700 (exp(lam_hi) scales the result)");
+        if (npairs > 0 && (!ei || !ej || !lo || !hi)) fail(KT_ERR_ARG, w + ": NULL argument");
+        for (int64_t p = 0; p < npairs; ++p)  // needs no matrix
+            if (ei[p] == ej[p])
+                fail(KT_ERR_ARG, w + ": a pair with i == j is a diagonal entry; kt_diag_fun_bracket bounds those");
+        if (!A) fail(KT_ERR_ARG, w + ": NULL argument");
+        if (A->n > INT32_MAX) fail(KT_ERR_ARG, w + ": n must fit 32-bit indices");
+        for (int64_t p = 0; p < npairs; ++p)
+            if (ei[p] < 0 || ei[p] >= A->n || ej[p] < 0 || ej[p] >= A->n)
+                fail(KT_ERR_ARG, w + ": pair index out of range");
+        if (A->ctx->ws.slq_submitted != A->ctx->ws.slq_collected)
+            fail(KT_ERR_ARG, w + ": kt_slq_submit calls are outstanding on this context");
+        require_symmetric(A, "ENTRIES_FUN_BRACKET:: symmetric A required");
+        if (!(rtol > 0.0)) rtol = 1e-10;
+        if (!(ftol > 0.0)) ftol = 1e-12;
+        if (it <= 0) it = (int)std::min<int64_t>(100, A->n);
+        if (npairs == 0) return KT_OK;
+        // (i, j) and (j, i) are one pair: both run as (min, max)
+        std::vector<int64_t> pi((size_t)npairs), pj((size_t)npairs);
+        for (int64_t p = 0; p < npairs; ++p) {
+            pi[p] = std::min(ei[p], ej[p]);
+            pj[p] = std::max(ei[p], ej[p]);
+        }
+        if (A->n <= 130) {
+            // dense path: exp(A)_ij = sum_k V_ik V_jk exp(w_k), on the host
+            const int n = (int)A->n;
+            std::vector<double> D((size_t)n * n, 0.0), wv(n), V((size_t)n * n);
+            for (int r = 0; r < n; ++r)
+                for (int64_t k = A->h_rowptr[r]; k < A->h_rowptr[r + 1]; ++k)
+                    D[r + (size_t)A->h_col[k] * n] = A->h_val[k];
+            sym_eig_host(n, D.data(), wv.data(), V.data());
+            for (int64_t p = 0; p < npairs; ++p) {
+                double s = 0.0;
+                for (int k = 0; k < n; ++k)
+                    s += V[(size_t)pi[p] + (size_t)k * n] * V[(size_t)pj[p] + (size_t)k * n] * std::exp(wv[k]);
+                lo[p] = hi[p] = s;
+                if (iter) iter[p] = 0;
+                if (flag) flag[p] = 0;
+                if (col_iter) col_iter[2 * p] = col_iter[2 * p + 1] = 0;
+            }
+            return KT_OK;
+        }
+        KT_HIP(hipSetDevice(A->ctx->device));
+        prof_recycle(A->ctx);
+        lanczos_pairs_bracket(A, npairs, pi.data(), pj.data(), lam_hi, rtol, ftol, it, lo, hi, iter, flag, col_iter);
     }
     KT_NODES_GUARD_END
 }

@@ -104,7 +104,10 @@ void ExplicitSweep::start() {
     hipStream_t st = L.st;
     if (unit_pos) {
         KT_HIP(hipMemsetAsync(ucur, 0, L.blk_bytes, st));
-        KT_HIP(launch_unit_start(n, P, ncols, unit_pos, ucur, sc, k2s, st));
+        if (pair_start)
+            KT_HIP(launch_pair_start(n, P, ncols / 2, unit_pos, ucur, sc, k2s, st));
+        else
+            KT_HIP(launch_unit_start(n, P, ncols, unit_pos, ucur, sc, k2s, st));
     } else if (!x) {
         KT_HIP(launch_rademacher(P, n, seed, probe_base, M.perm, ucur, st));
         KT_HIP(launch_fill(sc, P, 1.0 / std::sqrt((double)n), st));
@@ -133,6 +136,11 @@ void ExplicitSweep::use_basis_chunks(std::vector<DevMat>* chunks_, int spc_) {
 }
 
 void ExplicitSweep::use_unit_start(const int* pos_dev) { unit_pos = pos_dev; }
+
+void ExplicitSweep::use_pair_start(const int* pos_dev) {
+    unit_pos = pos_dev;
+    pair_start = true;
+}
 
 // basis slot j (nullptr: the sweep keeps no basis)
 double* ExplicitSweep::slot(int j) {
@@ -843,14 +851,16 @@ int lanczos_columns_adaptive(kt_matrix_s* A, const double* X, int ldx, int ncols
 // depend on (A, node, tol, it, fun) alone.
 //
 // node_sweeps is that driver with the check as a parameter, shared with the
-// bracket columns (§4.2i): check(record, m, P, j, nc, state, active, stream)
+// bracket columns (§4.2i) and the pair columns (§4.2j): start(sweep, pos) picks
+// the sweep's start block from its columns' rows (device, one per column);
+// check(record, m, P, j, nc, state, active, stream)
 // queues the stopping test of depth j on a lane; cut(t, d, alpha, off, beta_d)
 // forms column t's values from its record cut at its depth d (alpha: d, off:
 // d - 1 entries, beta_d the record's next off-diagonal), on the host pool.
 namespace {
 
-template <class Check, class Cut>
-void node_sweeps(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, int it, Check check, Cut cut) {
+template <class Start, class Check, class Cut>
+void node_sweeps(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, int it, Start start, Check check, Cut cut) {
     kt_context_s* ctx = A->ctx;
     const int64_t n = A->n;
     if (ncand < 1) return;
@@ -893,7 +903,7 @@ void node_sweeps(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, int it, Ch
             const int i = s0 + l, c0 = i * P, nc = std::min(P, ncols - c0);
             double* R = hr.as<double>() + (rec + stw) * i;
             ex.emplace_back(new ExplicitSweep(A, M, P, m, 0, 0, nullptr, 0, nc, nullptr, R, nullptr, nullptr, l, 0));
-            ex.back()->use_unit_start(dpos + c0);
+            start(*ex.back(), dpos + c0);
             KT_HIP(hipMemsetAsync(ctx->ws.adapt_state[l].ptr, 0, sizeof(double) * (stw + 1), ex.back()->stream()));
             polled[2 * l] = polled[2 * l + 1] = 1;
         }
@@ -970,7 +980,7 @@ void node_sweeps(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, int it, Ch
 void lanczos_nodes_adaptive(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, double tol, int it, int fun,
                             double* Xm, int* iter, int* lucky) {
     node_sweeps(
-        A, ncand, nodes, it,
+        A, ncand, nodes, it, [](ExplicitSweep& e, const int* pos) { e.use_unit_start(pos); },
         [=](const double* trec, int m, int P, int j, int nc, double* state, int* active, hipStream_t st) {
             return launch_node_check(trec, m, P, j, nc, fun, tol, state, active, st);
         },
@@ -989,7 +999,7 @@ void lanczos_nodes_bracket(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, 
                            double* lo, double* hi, int* iter, int* flag) {
     const double scale = std::exp(mu);
     node_sweeps(
-        A, ncand, nodes, it,
+        A, ncand, nodes, it, [](ExplicitSweep& e, const int* pos) { e.use_unit_start(pos); },
         [=](const double* trec, int m, int P, int j, int nc, double* state, int* active, hipStream_t st) {
             return launch_bracket_check(trec, m, P, j, nc, mu, rtol, state, active, st);
         },
@@ -1004,6 +1014,50 @@ void lanczos_nodes_bracket(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, 
             if (iter) iter[t] = d;
             if (flag) flag[t] = f;
         });
+}
+
+// The pair columns: node_sweeps over 2 npairs columns, pair
+// p's rows (i, j) at 2p and 2p + 1, with k_pair_start and k_pair_bracket_check.
+// The device decides depths; each column's sums come from the host rule on its
+// record cut at its own depth, and lo / hi / flag from pair_bracket_combine on
+// those times exp(mu), so a pair's results depend on (A, i, j, mu, rtol, ftol,
+// it) alone.
+void lanczos_pairs_bracket(kt_matrix_s* A, int64_t npairs, const int64_t* ei, const int64_t* ej, double mu,
+                           double rtol, double ftol, int it, double* lo, double* hi, int* iter, int* flag,
+                           int* col_iter) {
+    if (npairs < 1) return;
+    if (npairs > (INT32_MAX - kAdaptP) / 2) fail(KT_ERR_ARG, "the pair count must fit 32 bits");
+    const double scale = std::exp(mu);
+    std::vector<int64_t> rows((size_t)2 * npairs);
+    for (int64_t p = 0; p < npairs; ++p) {
+        rows[2 * p] = ei[p];
+        rows[2 * p + 1] = ej[p];
+    }
+    std::vector<double> L(rows.size()), U(rows.size());
+    std::vector<int> kind(rows.size()), dep(rows.size());
+    node_sweeps(
+        A, 2 * npairs, rows.data(), it, [](ExplicitSweep& e, const int* pos) { e.use_pair_start(pos); },
+        [=](const double* trec, int m, int P, int j, int nc, double* state, int* active, hipStream_t st) {
+            return launch_pair_bracket_check(trec, m, P, j, nc, mu, rtol, ftol, state, active, st);
+        },
+        [&](int t, int d, const double* al, const double* off, double beta_d) {
+            double l = 0.0, h = 0.0;
+            kind[t] = gauss_radau_sums(d, al, off, beta_d, mu, &l, &h);
+            L[t] = l * scale;
+            U[t] = h * scale;
+            dep[t] = d;
+        });
+    for (int64_t p = 0; p < npairs; ++p) {
+        const size_t a = (size_t)2 * p;
+        const int f = pair_bracket_combine(L[a], U[a], kind[a], L[a + 1], U[a + 1], kind[a + 1], rtol, ftol, &lo[p],
+                                           &hi[p]);
+        if (flag) flag[p] = f;
+        if (iter) iter[p] = std::max(dep[a], dep[a + 1]);
+        if (col_iter) {
+            col_iter[a] = dep[a];
+            col_iter[a + 1] = dep[a + 1];
+        }
+    }
 }
 
 static bool pow2_le128(int b) { return b >= 1 && b <= 128 && (b & (b - 1)) == 0; }

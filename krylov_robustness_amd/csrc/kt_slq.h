@@ -71,6 +71,10 @@ class ExplicitSweep : public Sweep {
     // array of rows in M's order, instead of the RNG's probes (kt_adapt.hip
     // k_unit_start).  Call before start().
     void use_unit_start(const int* pos_dev);
+    // The pair start (lanczos_pairs_bracket): ncols = 2 np columns, columns 2p
+    // and 2p + 1 start at (e_i + e_j) / sqrt 2 and (e_i - e_j) / sqrt 2 with i =
+    // pos[2p], j = pos[2p + 1] (kt_adapt.hip k_pair_start).  Call before start().
+    void use_pair_start(const int* pos_dev);
     void finish(int rows);
     const double* device_record() const { return trec; }
     hipStream_t stream() const { return L.st; }
@@ -80,6 +84,7 @@ class ExplicitSweep : public Sweep {
     std::vector<DevMat>* chunks = nullptr;
     int spc = 0;
     const int* unit_pos = nullptr;
+    bool pair_start = false;
     kt_matrix_s* A;
     const DevCSR& M;
     int P, m;
@@ -262,6 +267,19 @@ void lanczos_nodes_adaptive(kt_matrix_s* A, int64_t ncand, const int64_t* nodes,
 // rtol, it) only.  iter / flag nullable.  The context's stats 13-15 follow.
 void lanczos_nodes_bracket(kt_matrix_s* A, int64_t ncand, const int64_t* nodes, double mu, double rtol, int it,
                            double* lo, double* hi, int* iter, int* flag);
+
+// Gauss / Gauss-Radau bracket of exp(A)_ij, i != j: pair p
+// (0-based, i < j, repeats legal) takes two columns of those sweeps, started at
+// (e_i +- e_j) / sqrt 2, so a sweep holds 8 pairs; with L, U their Gauss and
+// Gauss-Radau sums, lo = (L+ - U-) / 2 <= exp(A)_ij <= hi = (U+ - L-) / 2.
+// kt_adapt.hip k_pair_bracket_check decides the depths; lo / hi / flag come
+// from pair_bracket_combine on gauss_radau_sums of each column's record cut at
+// its own depth (col_iter, nullable, 2 per pair), so they depend on (A, i, j,
+// mu, rtol, ftol, it) only.  iter: the deeper column's depth.  iter / flag
+// nullable.  The context's stats 13-15 follow.
+void lanczos_pairs_bracket(kt_matrix_s* A, int64_t npairs, const int64_t* ei, const int64_t* ej, double mu,
+                           double rtol, double ftol, int it, double* lo, double* hi, int* iter, int* flag,
+                           int* col_iter);
 
 // y-form sweep seeded by a device block (see kt_slq.cpp)
 void lanczos_sweep_y_block(kt_matrix_s* A, const DevCSR& M, int P, int m, const double* x, int ldx, int ncols,

@@ -744,6 +744,112 @@ def find_top_nodes_fun(A, num, ncand=None, nprobes=256, deflate=1, rtol=1e-10, m
     return cand[:num] + 1, {"lo": lo, "hi": hi, "candidates": cand + 1, "separated": separated}
 
 
+def entries_fun_bracket(A, pairs, rtol=1e-10, ftol=1e-12, it=None, lam_hi=None, ctx: Optional[Context] = None):
+    """Proved bounds lo[p] <= exp(A)[i, j] <= hi[p] on the communicability of
+    every row (i, j) of `pairs` ((npairs, 2) integers, 0-BASED as entries_fun
+    takes them; repeats and both orientations are legal, and (i, j) and (j, i)
+    return the same bits): half the difference of the Gauss / Gauss-Radau
+    brackets of the quadratic forms of exp at (e_i + e_j) / sqrt 2 and (e_i -
+    e_j) / sqrt 2 (kt_entries_fun_bracket).  Rows with i == j
+    are answered by diag_fun_bracket(rtol, it, lam_hi) and returned in place.
+    lam_hi must be an upper bound on lambda_max(A) (None: lambda_upper(A)); the
+    bounds are proved only if it is one.  f = exp only.  A row's values do not
+    depend on the other rows of the call.  Returns (lo, hi, iter, flag) arrays;
+    flag 0: lo and hi have one sign and hi - lo <= rtol min(|lo|, |hi|), 1:
+    both Krylov spaces ended, hi = lo is exact, 2: lam_hi is proved to be below
+    lambda_max, lo and hi are NaN (a diagonal row keeps its lo), 3: `it` steps
+    (None: min(100, n); at most 256) reached neither, the bracket is still
+    valid, 4: hi - lo <= ftol times the mean of the two quadratic forms, about
+    (exp(A)[i, i] + exp(A)[j, j]) / 2 -- the bracket has closed to the rounding
+    level of the method, the entry is smaller than that and all that is known
+    of it; such a bracket can be inverted by a few ulps of that scale."""
+    who = "entries_fun_bracket"
+    P = np.asarray(pairs)
+    if P.ndim != 2 or P.shape[1] != 2:
+        raise ValueError(f"{who}: pairs must have shape (npairs, 2), got {P.shape}")
+    if not np.issubdtype(P.dtype, np.integer):
+        raise ValueError(f"{who}: pairs must be integers, got {P.dtype}")
+    if it is not None and int(it) > 256:
+        raise _lib.KrylovError(_lib.KT_ERR_ARG, f"{who}: it must be at most 256")
+    n = A.n if isinstance(A, DeviceMatrix) else A.shape[0]
+    if P.size and (P.min() < 0 or P.max() >= n):
+        raise _lib.KrylovError(_lib.KT_ERR_ARG, f"{who}: pair index out of range (0-based, 0..{n - 1})")
+    if lam_hi is not None and not (np.isfinite(lam_hi) and float(lam_hi) <= 700.0):
+        raise _lib.KrylovError(_lib.KT_ERR_ARG, f"{who}: lam_hi must be finite and at most 700")
+    D = _dev(A, ctx)
+    if lam_hi is None:
+        # n <= 130 takes the dense host path, which has no use for a Radau node
+        lam_hi = lambda_upper(D, ctx=ctx) if n > 130 else 0.0
+    q = P.shape[0]
+    lo = np.zeros(q)
+    hi = np.zeros(q)
+    itr = np.zeros(q, dtype=np.int32)
+    fl = np.zeros(q, dtype=np.int32)
+    diag = P[:, 0] == P[:, 1]
+    off = np.flatnonzero(~diag)
+    if off.size:
+        ei, pi = _i64(P[off, 0])
+        ej, pj = _i64(P[off, 1])
+        olo, ohi = np.zeros(off.size), np.zeros(off.size)
+        oit, ofl = np.zeros(off.size, dtype=np.int32), np.zeros(off.size, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        _lib.check(_lib.load().kt_entries_fun_bracket(
+            D.handle, off.size, pi, pj, float(lam_hi), float(rtol), float(ftol), int(it or 0), _dptr(olo),
+            _dptr(ohi), oit.ctypes.data_as(ip), ofl.ctypes.data_as(ip), None))
+        lo[off], hi[off], itr[off], fl[off] = olo, ohi, oit, ofl
+    if diag.any():
+        lo[diag], hi[diag], itr[diag], fl[diag] = diag_fun_bracket(D, P[diag, 0] + 1, rtol=rtol, it=it,
+                                                                   lam_hi=lam_hi, ctx=D.ctx)
+    return lo, hi, itr, fl
+
+
+def find_top_edges_bracket(A, num, ncand=None, nprobes=256, deflate=1, rtol=1e-10, ftol=1e-12, m=30, seed=0,
+                           it=None, lam_hi=None, ctx: Optional[Context] = None):
+    """The top `num` existing edges by communicability exp(A)[i, j] with a
+    proved order among the candidates, the edge twin of find_top_nodes_fun:
+    rank every edge of find(tril(A, -1)) by the stochastic estimate
+    entries_fun(nprobes, m, seed, deflate=deflate).mean (find_top_edges_fun's
+    ranking), bracket the first `ncand` of it (default 4 num) with
+    entries_fun_bracket(rtol, ftol, it, lam_hi) and return the first `num` of
+    them by descending lower bound, ties in find(tril(A, -1)) order; 1-based
+    with i > j, as find_top_edges returns them, so the result serves as
+    greedy_krylov(..., top=...).  The same warning / error when fewer than
+    `num` edges exist.
+
+    Returns (edges, info): info "candidates" ((ncand, 2), 1-based, i > j, in
+    the bracketed order), "lo" and "hi" in that order, and "separated": True
+    when every lo[r] > hi[r + 1] over all bracketed candidates, so their order
+    is proved.  That proof covers the candidate set only: an edge the stochastic
+    ranking left out of it is bounded by nothing here, and may belong among the
+    returned ones; 256 probes leave the estimate several per cent off per
+    entry, so where the top edges are nearly tied raise nprobes and ncand until
+    the candidate set holds every edge within a few standard errors
+    (entries_fun(...).stderr) of the num-th value.
+    f = exp only."""
+    from .core import _deflate_arg, entries_fun
+    deflate = _deflate_arg("find_top_edges_bracket", deflate, A)
+    D = _dev(A, ctx)
+    I, J = _tril_edges(D.to_scipy())
+    if len(I) < num:
+        warnings.warn("FIND_TOP_EDGES:: there are not enough edges in the graph")
+    num = int(np.floor(num))
+    if len(I) < num:
+        raise IndexError("FIND_TOP_EDGES:: there are not enough edges in the graph")
+    if len(I) == 0:
+        return np.zeros((0, 2), dtype=np.int64), {"lo": np.zeros(0), "hi": np.zeros(0),
+                                                   "candidates": np.zeros((0, 2), dtype=np.int64), "separated": True}
+    ncand = min(len(I), max(num, 4 * num if ncand is None else int(ncand)))
+    est = entries_fun(D, np.stack([I, J], axis=1), nprobes, m=m, seed=seed, fun="exp", deflate=deflate, ctx=ctx)
+    cand = _stable_head(-np.asarray(est.mean, dtype=np.float64), ncand)
+    lo, hi, _, _ = entries_fun_bracket(D, np.stack([I[cand], J[cand]], axis=1), rtol=rtol, ftol=ftol, it=it,
+                                       lam_hi=lam_hi, ctx=D.ctx)
+    order = np.lexsort((cand, -lo))
+    cand, lo, hi = cand[order], lo[order], hi[order]
+    separated = bool(np.all(lo[:-1] > hi[1:])) if ncand > 1 else True
+    E = np.stack([I[cand] + 1, J[cand] + 1], axis=1)
+    return E[:num], {"lo": lo, "hi": hi, "candidates": E, "separated": separated}
+
+
 def find_top_nodes_miobi(A, num, t=25, tol=0.0, max_spmm=0, seed=0, ctx: Optional[Context] = None):
     """The top `num` nodes ranked by ascending MIOBI node score (the node
     miobi_break_node would remove first comes first) from the leading t

@@ -1628,21 +1628,7 @@ __global__ __launch_bounds__(256) void k_scatter_elems(int64_t count, const int6
 // active = 1 while the stage runs; every kernel of a term (the SpMM through
 // its skip flag, k_expmv_term, k_expmv_check) is a no-op once active = 0.
 // ---------------------------------------------------------------------------
-// term maxima of the fused expmv path: 64 slots per term, one 128-B line
-// each (workgroup b folds into slot b % 64), so same-address atomics stay few
-// (config 1: 340 workgroups, 31k at n = 1M)
-constexpr int kTermSlots = 64, kTermSlotStride = 16;
-struct ExpmvState {
-    int active;
-    int mv;
-    double c1;
-    double c1s[2];  // fused path: c1 of the check of term j in c1s[j & 1]
-    // fused path: term j's row-sum maxima of |b| and |f| in set j % 3, as
-    // the bit patterns of the (non-negative) doubles, so an unsigned atomic
-    // max is the exact fmax; term j zeroes set (j + 1) % 3 for the next
-    // term, k_expmv_begin set 1 for a stage's first term
-    unsigned long long term_max[3][kTermSlots][kTermSlotStride];
-};
+// (ExpmvState, kTermSlots, kTermSlotStride: kt_launch.h)
 
 // stage start: c1 = norm(b, inf) from k_inf_norm partials; active = 1   (:73)
 __global__ __launch_bounds__(256) void k_expmv_begin(const double* __restrict__ partial, int nb,
@@ -2800,6 +2786,8 @@ static int expmv_rows_grid(int n_tasks_hint) {
     if (g > n_tasks_hint) g = n_tasks_hint;
     return g < 1 ? 1 : g;
 }
+
+int expmv_rows_blocks(int tasks) { return expmv_rows_grid((tasks + kExpmvRowsWaves - 1) / kExpmvRowsWaves); }
 
 hipError_t launch_expmv_step(int P, bool unit, const CsrView& M, const int* med_rows, int n_med, int nc,
                              int ld, double mu, double coef, double tol, int k, const double* bin,

@@ -410,6 +410,21 @@ hipError_t launch_inf_norm(int n, int nc, const double* X, int ldx, double* part
 // expmv Taylor stage with the stop test on the device (state: expmv_state_bytes();
 // layout {int active; int mv; double c1;}); partial: 2 * inf_norm_blocks() doubles
 size_t expmv_state_bytes();
+// term maxima of the fused expmv path: 64 slots per term, one 128-B line
+// each (workgroup b folds into slot b % 64), so same-address atomics stay few
+// (config 1: 340 workgroups, 31k at n = 1M)
+constexpr int kTermSlots = 64, kTermSlotStride = 16;
+struct ExpmvState {
+    int active;
+    int mv;
+    double c1;
+    double c1s[2];  // fused path: c1 of the check of term j in c1s[j & 1]
+    // fused path: term j's row-sum maxima of |b| and |f| in set j % 3, as
+    // the bit patterns of the (non-negative) doubles, so an unsigned atomic
+    // max is the exact fmax; term j zeroes set (j + 1) % 3 for the next
+    // term, k_expmv_begin set 1 for a stage's first term
+    unsigned long long term_max[3][kTermSlots][kTermSlotStride];
+};
 hipError_t launch_expmv_begin(const double* partial, int nb, void* state, hipStream_t st);
 hipError_t launch_expmv_term(int n, int nc, double mu, double coef, const double* Ab, double* b,
                              double* F, int ld, double* partial, const void* state, hipStream_t st);
@@ -419,6 +434,9 @@ hipError_t launch_expmv_check(int n, const double* partial, double tol, void* st
 // of term k's row sums folded into the state (term_max slot k % 3)
 // waves: per block (0: the per-term kernel's)
 int expmv_step_blocks(int n, int P, int n_long, int n_med, int waves = 0);
+// the grid of forms 2 and 3 (k_expmv_rows) for tasks = n_long + n_med +
+// ceil(n_short / 8): a workgroup per 4 tasks, at most the resident workgroups
+int expmv_rows_blocks(int tasks);
 // the default form of launch_expmv_step for this shape (true: SPLIT, grids
 // above 1,024 workgroups); with split the host launches
 // launch_expmv_slot_check after every term but a stage's last.
